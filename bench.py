@@ -2,6 +2,7 @@
 """Headline benchmark: pair-interactions/s of the Laplace single-layer N x N direct sum on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload laplace_sl|laplace_sldl|stokeslet|helmholtz|laplace_sl_f32|stokeslet_f32|laplace_sl_16k|p2p_lists|near_apply]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full evaluation of the hot path over one synthetic point cloud that is already resident in HBM:
@@ -10,7 +11,12 @@ At N = 1 the workload is BASELINE.json's headline: Laplace3D single layer, 2^20 
 For N > 1 the SAME problem is split: targets are block-partitioned over the ranks, sources replicated, one RCCL
 all-gather of the potential slabs per step (strong scaling: north_star asks for >= 6x at 8 GPUs on this problem).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` and, at N = 1, `cpu_baseline`.
+Rank 0 prints ONE JSON line, `roofline` included.  A plain run does only what that line's headline
+needs: set-up, warm-up, the timed steps.  --full adds the informational legs, all outside the timed region and none part of `value`:
+`cpu_baseline` (N = 1), the headline at the reference callers' accuracy (`at_reference_callers_accuracy`, fp64 at N = 1) and, for
+near_apply, the whole ComputePotential from host arrays (`compute_potential_from_host`).
+--dump-outputs DIR writes what the last timed step computed — the potential a caller of the timed path receives — as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +40,20 @@ WORKLOADS = {
     "laplace_sl_16k": ("Laplace3D-FxU", 1 << 14, "f64", "Laplace3D single layer, 2^14 x 2^14, fp64 [BASELINE configs[0], the reference's CPU-runnable case]"),
 }
 PEAK_TFLOPS = {"f64": 78.6, "f32": 157.3}   # vector FMA peaks, BASELINE.md §3 / MI355X_MICROARCH.md chip table
+DUMP_BYTES = 64 << 20                        # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor or array} -> out_dir/<name>.npy, flat, in the dtype computed (fp64 or fp32).  Should the arrays
+    together exceed DUMP_BYTES, each is cut to a fixed, seeded sample of its entries (in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_impl():
@@ -151,6 +171,8 @@ def bench_near(args):
     e1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - tic
+    if args.dump_outputs:            # U after the last step (the operator accumulates into it: warm-up and timed applications)
+        dump_outputs(args.dump_outputs, {"potential": U})
     k_ms = e0.elapsed_time(e1) / args.steps
     entries = op.operator_bytes / 8
     achieved = op.operator_bytes / (k_ms * 1e-3) / 1e9
@@ -161,6 +183,14 @@ def bench_near(args):
                                    (nelem, nds * k0, near * k1, op.operator_bytes / 1e9, ntrg), "workgroups": op.workgroups},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": read_traffic("near_apply"),
                          "kernel_ms": k_ms, "note": "algorithmic bytes = sizeof(K_near): 8 B per operator entry, read once per application"}}
+    if args.full:
+        bench_near_full(args, line, rng, op, K, order, cnt, dsp, nelem, nds, near, k0, k1, ntrg)
+    print(json.dumps(line), flush=True)
+
+
+def bench_near_full(args, line, rng, op, K, order, cnt, dsp, nelem, nds, near, k0, k1, ntrg):
+    """The --full legs of near_apply, outside the timed region: the whole ComputePotential from host arrays and the CPU baseline."""
+    import sctl_amd
     # Informational, outside the timed region: the whole BoundaryIntegralOp::ComputePotential (boundary_integral.txx:608-614) for this operator
     # from HOST arrays, as a C++ caller has them — far field (Stokeslet over the elements' nodes as far-field quadrature) + this near field.
     # "fused": sctl_amd_op_eval_potential (densities down once, near field added to the far field on the device, potential up once);
@@ -205,7 +235,6 @@ def bench_near(args):
         secs = time.perf_counter() - t0
         line["cpu_baseline"] = {"value": reps * Kb.size / secs, "unit": "matrix-entries/s", "cores": physical_cores(), "threads": os.cpu_count(), "kind": "port",
                                 "sample": "%d of %d element blocks, numpy (BLAS) GEMV per block, %d repetitions, %.1f s" % (sample, nelem, reps, secs)}
-    print(json.dumps(line), flush=True)
 
 
 def bench_lists(args):
@@ -249,6 +278,8 @@ def bench_lists(args):
         e1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - tic
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"potential": u})
     k_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     fpp = sctl_amd.flops_per_pair(kernel)
     achieved = plan.pairs * fpp / (k_ms * 1e-3) / 1e12
@@ -261,7 +292,7 @@ def bench_lists(args):
             "roofline": {"bound": "mfma", "pipe": "fp64 VALU", "achieved": achieved, "peak": PEAK_TFLOPS["f64"], "unit": "TFLOP/s", "frac": achieved / PEAK_TFLOPS["f64"],
                          "traffic": read_traffic("p2p_lists"), "flops_per_pair": fpp, "kernel_ms": k_ms,
                          "note": "vector-FMA bound: algorithmic flops = listed pairs x (3 + FLOPS() + 2 K0 K1); one launch per step"}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from concurrent.futures import ThreadPoolExecutor
         R = cpu_impl()
         nthreads = min(os.cpu_count() or 1, 32)
@@ -313,7 +344,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="laplace_sl", choices=sorted(WORKLOADS) + ["near_apply", "p2p_lists"])
     ap.add_argument("--digits", type=int, default=-1, help="accuracy request; -1 = full precision (the reference default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the informational legs outside the timed steps (CPU baseline, the headline at 10 digits, near_apply's host-array ComputePotential)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64 or float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -412,10 +446,12 @@ def main():
     tic = time.perf_counter()
     whole[0].record()
     for _ in range(args.steps):
-        step(True)
+        last = step(True)
     whole[1].record()
     fence()
     elapsed = time.perf_counter() - tic
+    if args.dump_outputs and rank == 0:      # the whole potential in the caller's target order (the all-gathered one for N > 1)
+        dump_outputs(args.dump_outputs, {"potential": last})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -478,7 +514,7 @@ def main():
             # the same problem on ONE such GPU would take about this long (work is linear in the slab): compare with the N = 1 record
             line["n1_equiv_ms"] = slowest * world
             line["kernel_ms_slowest_rank"] = slowest
-        if world == 1 and args.digits < 0 and dtype == "f64":
+        if args.full and world == 1 and args.digits < 0 and dtype == "f64":
             # Informational, outside the timed region and not part of `value`: the same workload at the accuracy the reference's
             # own callers ask for — ParticleFMM defaults to 10 digits (fmm-wrapper.txx:204), BoundaryIntegralOp to tol 1e-10 (:500).
             full = op.eval_slab(r_trg, r_src, n_src, v_src).clone()          # the full-precision result, to measure the 10-digit one against
@@ -501,7 +537,7 @@ def main():
                                                                              "3/2 d^2 <= 4.3e-15 relative; the MEAN of that one-sided error (-1.7e-16) is folded into the per-target scale, "
                                                                              "leaving mean +5e-17, rms 3.1e-16, range [-4.1e-15, +4.7e-16] (profiles/r03_rsq_refine_accuracy.txt), for every "
                                                                              "digits in 8..14; the default (full-precision) mode measures max 2.4 ulp, rms 0.66 ulp per pair, the reference's own default max 2.5 ulp, rms 0.77 ulp"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(kernel, N, dtype)
             except Exception as e:   # the baseline is reported, never required for the GPU number

@@ -224,7 +224,17 @@ def dropin():
     include/sctl_amd/sctl_dropin.hpp, so that their arithmetic runs in libsctl_amd.so: oracle/ref_shim.cpp with -DSCTL_REF_DROPIN.
     Needs a GPU to evaluate anything.  None if oracle/_ref holds no such build."""
     path = os.path.join(_HERE, "_ref", "libsctl_ref_dropin.so")
-    return Reference(path) if os.path.exists(path) else None
+    if not os.path.exists(path):
+        return None
+    _load_product()
+    return Reference(path)
+
+
+def _load_product():
+    """A drop-in shim needs libsctl_amd.so: load it first (sctl_amd.lib(), by its full path), so that the shim's dependency binds to
+    that copy by its soname, wherever oracle/_ref lies."""
+    import sctl_amd
+    sctl_amd.lib()
 
 
 def rel_l2(a, b):
@@ -244,6 +254,8 @@ def reference_near(name, xt, xn_trg, xs, xn, wts, f, trg_normal_dot_prod=False, 
     Returns u_total (ComputePotential), u_near (ComputeNearInterac alone) and the near-operator arrays SetupNear built.
     free_nodes > 0: TWO element lists — the last `free_nodes` nodes form a second, matrix-free list (sctl_ref_boundary_near2)."""
     path = os.path.join(_HERE, "_ref", "libsctl_ref_near_dropin.so" if dropin else "libsctl_ref_near.so")   # dropin: kernels = sctl_amd::HipKernel
+    if dropin:
+        _load_product()
     lib = C.CDLL(path)
     if dropin and dropin_devices is not None:
         set_dropin_devices(lib, dropin_devices, 0)
