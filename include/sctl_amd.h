@@ -186,6 +186,34 @@ int sctl_amd_op_set_target_normals(sctl_amd_op* op, const void* n_trg);
 int sctl_amd_op_eval(sctl_amd_op* op, const void* v_src, void* v_trg, int accumulate, int digits, const void* ctx, int ctx_bytes);
 void sctl_amd_op_destroy(sctl_amd_op* op);
 
+/* ---- several densities against one geometry (block Krylov solves, several incident fields, the six rigid motions of a body) -------- */
+/* nd densities on the same sources and targets in one evaluation: what nd calls of the single-density entry compute, with the work of a
+ * pair that does not depend on the density (distance, reciprocal square root, Helmholtz's e^{ikr}) done once for several densities.
+ * Layout is DENSITY-MAJOR: v_src holds nd consecutive density vectors, [nd][Ns*SrcDim], and v_trg [nd][Nt*TrgDim]; row m is exactly
+ * what a single-density call takes and returns.  nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, and nd == 1 IS the
+ * single-density entry (bit-identical results).  Argument errors return the codes of sctl_amd_eval_host, before any device work.
+ * The built-in kernels run up to 8 densities (4 for the Stokes kernels with 4 outputs or inputs, the traction and the fused Laplace
+ * kernel) per pass on the exact all-pairs kernel; a plugin kernel is evaluated one density at a time on the same stream (correct, no
+ * faster).  Counters grow by what nd single calls add.
+ * Accuracy: fp64 as the single-density exact kernel at every `digits` (mode_for: seed, Newton, cubic step).  fp32 always runs the exact
+ * vector-pipe pair here — there is no matrix-core or tile-centred form of several densities — so an fp32 result has full fp32 accuracy
+ * (~5e-7 relative per pair) at every `digits`, also where a single-density call at digits <= 7 would take the bf16 matrix cores. */
+/* DEVICE arrays; enqueued on `stream`, accumulated into v_trg. */
+int sctl_amd_eval_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                   const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, void* stream);
+/* HOST arrays, one device; returns when v_trg (accumulated into) is final. */
+int sctl_amd_eval_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                 const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device);
+/* The operator's far field (as sctl_amd_op_eval) for nd densities, HOST arrays v_src[nd][Ns*SrcDim], v_trg[nd][Nt*TrgDim] (TrgDim/3 with
+ * target normals); source weights and target normals apply to every density; any device list. */
+int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void* v_trg, int accumulate, int digits, const void* ctx, int ctx_bytes);
+/* The plan of such a call (no side effects, no GPU needed): densities per pass of the widest pass and the number of passes (the last pass
+ * takes the narrowest form that holds what is left, one density the 2-density form), and of the first pass the targets per lane, source splits, workgroups over all its target
+ * launches, and the largest partial-sum workspace of any pass.  The partial sums of one launch stay within 2 GB: a pass cuts its targets
+ * into several launches rather than take fewer source splits than the L2 rule asks for.  nd == 1 is sctl_amd_eval_plan's answer. */
+int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* densities_per_pass, int* passes,
+                                 int* trg_per_lane, int* src_splits, int64_t* workgroups, int64_t* workspace_bytes);
+
 /* ---- rank-parallel evaluation: one process per GPU (ParticleFMM::EvalDirect under MPI, fmm-wrapper.txx:504-561) --------------- */
 /* The reference partitions targets and sources over MPI ranks and rotates the source blocks round a ring (:537-558).  Here every
  * rank keeps ITS targets, and the sources (and, per evaluation, the densities) of ALL ranks are all-gathered into each rank's

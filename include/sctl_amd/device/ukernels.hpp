@@ -13,6 +13,13 @@
 //   FLOPS, scale()      kernel_functions.hpp FLOPS() / uKerScaleFactor
 //   pack(rec, x, n, f)  build the LDS record of one source from the AoS inputs
 //   pair<R,MODE,MASKED>(acc, d, rec, ctx, K)   one pair interaction, d = x_trg - x_src  (generic-kernel.txx:83)
+// and the multi-density forms used by sctl_amd/csrc/multi_kernel.hpp (M densities on the same sources and targets):
+//   NREC_M<M>                  reals per LDS record: x, the normal where ND > 0, then M densities of K0 reals (pack_multi), padded to 16 bytes
+//   pack_m<R,M>(rec, x, n, f)  f[M][K0]: the record holds the geometry once and the densities as they are (no density is pre-multiplied
+//                              into the geometry: a double-layer record keeps n and applies each f in pair_m)
+//   pair_m<R,MODE,MASKED,M>(acc, d, rec, ctx, K)   acc[M][K1]: the density-independent factors of the pair (distance, reciprocal square root
+//                              and its refinement, Helmholtz's e^{ikr}) once, then one contraction per density.  Same masking and acc_factor
+//                              as pair(): a launch scales both forms alike.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -306,6 +313,24 @@ template <int MODE, int P, bool MASKED, class R> __device__ __forceinline__ R rs
 // (exact) for the Newton step, A^2 (A has 24 bits: exact) for the cubic step, 1 for the bare seed.
 constexpr double rsqrt_scaled_c2(int mode) { return rsqrt_scaled_factor(mode, 1) == 1 ? 1.0 : mode == 1 ? 4.0 : cubic83_factor(1) * cubic83_factor(1); }
 
+
+// ---- multi-density records (pack_m / pair_m of every struct below) -------------------------------------------------
+constexpr int nrec_multi(int nd, int k0, int m) { return (3 + nd + m * k0 + 1) / 2 * 2; }
+template <int ND, int K0, class R, int M> __device__ __forceinline__ void pack_multi(R* rec, const R* x, const R* n, const R (&f)[M][K0]) {
+  rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2];
+#pragma unroll
+  for (int k = 0; k < ND; k++) rec[3 + k] = n[k];
+#pragma unroll
+  for (int m = 0; m < M; m++)
+#pragma unroll
+    for (int k = 0; k < K0; k++) rec[3 + ND + m * K0 + k] = f[m][k];
+}
+#define SCTL_AMD_MULTI_RECORD                                                                                                          \
+  template <int M> static constexpr int NREC_M = nrec_multi(ND, K0, M);                                                               \
+  template <class R, int M> static __device__ __forceinline__ void pack_m(R* rec, const R* x, const R* n, const R (&f)[M][K0]) {      \
+    pack_multi<ND, K0>(rec, x, n, f);                                                                                                 \
+  }
+
 // ---- Laplace single layer: u = f / r          (kernel_functions.hpp:15-31) -------------------------------
 struct Laplace3D_FxU {
   static constexpr int ID = 0, K0 = 1, K1 = 1, ND = 0, NREC = 4, FLOPS = 6;
@@ -319,6 +344,13 @@ struct Laplace3D_FxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair(R (&acc)[K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
     const R rinv = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);   // MODE 1: 2/r, MODE 2: (8/3)/r
     acc[0] = fma_(rec[3], rinv, acc[0]);
+  }
+  // multi: 1 FMA per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R rinv = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[3 + m], rinv, acc[m][0]);
   }
 };
 
@@ -335,6 +367,13 @@ struct Laplace3D_DxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair(R (&acc)[K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(dot3(d, rec + 3), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq), acc[0]);
   }
+  // multi: the record keeps n, each density is one FMA on (r.n) / r^3
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R t = dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq);
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[6 + m], t, acc[m][0]);
+  }
 };
 
 // ---- gradient of the Laplace single layer: u_j = f r_j / r^3, scale -1/(4 pi)   (kernel_functions.hpp:53-72)
@@ -350,6 +389,16 @@ struct Laplace3D_FxdU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair(R (&acc)[K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
     const R t = rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq) * rec[3];
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
+  }
+  // multi: r / r^3 once, 3 FMAs per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R t = rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq);
+    const R td[3] = {t * d[0], t * d[1], t * d[2]};
+#pragma unroll
+    for (int m = 0; m < M; m++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(rec[3 + m], td[j], acc[m][j]);
   }
 };
 
@@ -371,6 +420,21 @@ struct Stokes3D_FxU {
     const R t = dot3(d, rec + 3) * (y * y);                                                  // C^2 (r.f) / r^2
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[6 + j]), acc[j]);         // C^3 (f_j + r_j (r.f) / r^2) / r: 1/r^3 is never formed
   }
+  // multi: C^3 (f_j / r + (r.f) r_j / r^3) with r / r^3 and 1/r formed once; 9 instructions per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);                                  // C / r
+    const R y3 = (y * y) * y;
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));           // C^2 (C / r): the term in 1/r alone
+    const R e[3] = {y3 * d[0], y3 * d[1], y3 * d[2]};                                         // C^3 r / r^3
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* f = rec + 3 + 3 * m;
+      const R rf = dot3(d, f);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
+    }
+  }
 };
 
 // ---- stresslet: u_j = r_j (r.f)(r.n) / r^5, scale 3/(4 pi)   (kernel_functions.hpp:97-120) ----------------
@@ -387,6 +451,18 @@ struct Stokes3D_DxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair(R (&acc)[K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
     const R t = dot3(d, rec + 3) * dot3(d, rec + 6) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
+  }
+  // multi: (r.n) r / r^5 once, (r.f) and 3 FMAs per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R g = dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    const R gd[3] = {g * d[0], g * d[1], g * d[2]};
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R rf = dot3(d, rec + 6 + 3 * m);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(gd[j], rf, acc[m][j]);
+    }
   }
 };
 
@@ -405,6 +481,28 @@ struct Stokes3D_FxT {
     for (int j = 0; j < 3; j++) {       // u_jk = u_kj: the upper triangle only (6 FMAs instead of 9); finish() fills in the rest
       const R tj = t * d[j];
       for (int k = j; k < 3; k++) acc[j * 3 + k] = fma_(tj, d[k], acc[j * 3 + k]);
+    }
+  }
+  // multi: the six r_j r_k / r^5 once, (r.f) and 6 FMAs per density (upper triangle; finish() per density)
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R p = rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    R dd[6];
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const R pj = p * d[j];
+#pragma unroll
+      for (int k = j; k < 3; k++) dd[q++] = pj * d[k];
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R rf = dot3(d, rec + 3 + 3 * m);
+      int i = 0;
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+#pragma unroll
+        for (int k = j; k < 3; k++, i++) acc[m][j * 3 + k] = fma_(dd[i], rf, acc[m][j * 3 + k]);
     }
   }
   template <class R> static __device__ __forceinline__ void finish(R (&acc)[K1]) { acc[3] = acc[1]; acc[6] = acc[2]; acc[7] = acc[5]; }
@@ -427,6 +525,21 @@ struct Stokes3D_FSxU {
     const R t = fma_(d[2], rec[5], fma_(d[1], rec[4], fma_(d[0], rec[3], rec[6]))) * (y * y);               // C^2 ((r.f) + f_3) / r^2
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[7 + j]), acc[j]);
   }
+  // multi: as the Stokeslet's, with f_3 in the dot product
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);                                  // C / r
+    const R y3 = (y * y) * y;
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));           // C^2 (C / r): the term in 1/r alone
+    const R e[3] = {y3 * d[0], y3 * d[1], y3 * d[2]};                                         // C^3 r / r^3
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* f = rec + 3 + 4 * m;
+      const R rf = fma_(d[2], f[2], fma_(d[1], f[1], fma_(d[0], f[0], f[3])));
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
+    }
+  }
 };
 
 // ---- velocity + pressure: Stokeslet and p = (r.f) / r^3   (kernel_functions.hpp:174-198) -------------------
@@ -446,6 +559,22 @@ struct Stokes3D_FxUP {
     const R t = dot3(d, rec + 3) * (y * y);
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[6 + j]), acc[j]);
     acc[3] = fma_(t, y, acc[3]);
+  }
+  // multi: the Stokeslet's form plus the pressure (r.f) C^3 / r^3, 10 instructions per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);                                  // C / r
+    const R y3 = (y * y) * y;
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));           // C^2 (C / r): the term in 1/r alone
+    const R e[3] = {y3 * d[0], y3 * d[1], y3 * d[2]};                                         // C^3 r / r^3
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* f = rec + 3 + 3 * m;
+      const R rf = dot3(d, f);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
+      acc[m][3] = fma_(y3, rf, acc[m][3]);
+    }
   }
 };
 
@@ -481,6 +610,31 @@ struct Laplace3D_FDxUdU {
     acc[0] = fma_(w, y, fma_(rec[9], y, acc[0]));           // C^3 (q / r + mu (r.n) / r^3)
     const R c = fma_(w, K.c3, rec[9]);                      // C^2 (q + 3 mu (r.n) / r^2)
     for (int j = 0; j < 3; j++) acc[1 + j] = fma_(y3, fma_(-d[j], c, rec[6 + j]), acc[1 + j]);   // C^5 (m_j - r_j c) / r^3
+  }
+  // multi: the record keeps n and (q, mu) per density.  With y = C / r, c2 = C^2 and dn = r.n, pair() accumulates
+  //   u      += c2 q y + mu dn y^3                              (finish_mode multiplies by c2)
+  //   grad_j += mu (c2 y^3 n_j - 3 dn y^5 r_j) - q c2 y^3 r_j
+  // so the five factors in brackets are formed once and each density costs 8 FMAs.
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);   // C / r
+    const R y2 = y * y;
+    const R y3 = y2 * y;
+    const R dn = dot3(d, rec + 3);
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));
+    const R y3c = (rsqrt_scaled_c2(MODE) == 1.0) ? y3 : y3 * R(rsqrt_scaled_c2(MODE));
+    const R g1 = dn * y3;
+    const R a = (dn * y2) * K.c3 * y3;                      // 3 dn y^5
+    R A[3], B[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) { A[j] = fma_(y3c, rec[3 + j], -a * d[j]); B[j] = y3c * d[j]; }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R q = rec[6 + 2 * m], mu = rec[7 + 2 * m];
+      acc[m][0] = fma_(g1, mu, fma_(yc, q, acc[m][0]));
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][1 + j] = fma_(A[j], mu, fma_(-B[j], q, acc[m][1 + j]));
+    }
   }
   template <class R, int MODE> static __device__ __forceinline__ void finish_mode(R (&acc)[K1]) { acc[0] *= R(rsqrt_scaled_c2(MODE)); }
 };
@@ -518,6 +672,31 @@ struct Helmholtz3D_FxU {
     const R gr = amp * cs, gi = amp * sn;
     acc[0] = fma_(gr, rec[3], fma_(-gi, rec[4], acc[0]));
     acc[1] = fma_(gi, rec[3], fma_(gr, rec[4], acc[1]));
+  }
+  // multi: G = e^{ikr} / r as pair() forms it, once; 4 FMAs per density
+  SCTL_AMD_MULTI_RECORD
+  template <class R, int MODE, bool MASKED, int M, int VARIANT = 0> static __device__ __forceinline__ void pair_m(R (&acc)[M][K1], const R (&d)[3], const R* rec, const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R fr = rec[3 + 2 * m], fi = rec[4 + 2 * m];
+      acc[m][0] = fma_(gr, fr, fma_(-gi, fi, acc[m][0]));
+      acc[m][1] = fma_(gi, fr, fma_(gr, fi, acc[m][1]));
+    }
   }
   // fp64, one reduction of r for the whole factor e^{ikr} (fastmath.hpp: cexp_tab_k); returns G = e^{ikr} / r.  The speculative pass runs it
   // unconditionally and records the largest distance; the careful pass branches per pair to libm beyond the table's range.

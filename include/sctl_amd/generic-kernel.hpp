@@ -137,6 +137,28 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_lists_host");
   }
 
+  // Several densities on the same sources and targets in one evaluation (sctl_amd_eval_densities_host; not in the reference, whose callers
+  // call Eval once per density): row m of F (nd x Ns*SrcDim) is a density, row m of U (nd x Nt*TrgDim) its potential — what Eval gives for
+  // that row, with the density-independent work of a pair done once for several rows.  U follows Eval's rule: the right size is accumulated
+  // into, any other is resized and zeroed.  nd == 1 is Eval's own path.  fp32 runs the exact vector-pipe pair (full fp32 accuracy at every digits).
+  template <class Real, Integer digits = -1>
+  void EvalDensities(Matrix<Real>& U, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Matrix<Real>& F) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nd = F.Dim(0);
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(F.Dim(1) == Ns * KDIM0);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(nd <= 0x7fffffff);
+    if (U.Dim(0) != nd || U.Dim(1) != Nt * KDIM1) {
+      U.ReInit(nd, Nt * KDIM1);
+      U.SetZero();
+    }
+    RequireSupported();
+    const int rc = sctl_amd_eval_densities_host(DeviceKernelId(), RealTag<Real>::value, (int)nd, Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr,
+                                                F.begin(), U.begin(), (int)digits, ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_densities_host");
+  }
+
  private:
   static void RequireSupported() {
     if (!IsSupported()) {

@@ -28,7 +28,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_near_apply_device", "sctl_amd_near_info", "sctl_amd_near_destroy", "sctl_amd_num_kernels", "sctl_amd_register_kernel", "sctl_amd_load_plugin",
            "sctl_amd_set_debug", "sctl_amd_comm_create", "sctl_amd_comm_info", "sctl_amd_comm_allgatherv_host", "sctl_amd_comm_barrier", "sctl_amd_comm_selftest", "sctl_amd_comm_destroy",
            "sctl_amd_op_set_sources_dist", "sctl_amd_op_eval_dist", "sctl_amd_op_set_near", "sctl_amd_op_eval_potential", "sctl_amd_lists_create", "sctl_amd_lists_eval_device", "sctl_amd_lists_eval_host", "sctl_amd_lists_info", "sctl_amd_lists_destroy",
-           "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host"]
+           "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host", "sctl_amd_eval_densities_device", "sctl_amd_eval_densities_host", "sctl_amd_op_eval_densities",
+           "sctl_amd_eval_densities_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -117,6 +118,10 @@ def lib():
     L.sctl_amd_lists_destroy.restype = None
     L.sctl_amd_eval_lists_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_eval_lists_device.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
+    L.sctl_amd_op_eval_densities.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sctl_amd_eval_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(i64)] * 2
     _LIB = L
     return L
 
@@ -202,6 +207,15 @@ def plan(name, real, Nt, Ns, digits=-1, nt_whole=0):
                 pipe="bf16 matrix cores (r^2) + vector pipe (rsqrt, accumulate)" if pipe == 2 else "vector pipe")
 
 
+def plan_densities(name, real, nd, Nt, Ns, digits=-1):
+    """Launch plan of an nd-density evaluation (sctl_amd_eval_densities_plan): densities per pass, passes, and of the first pass targets per
+    lane, source splits, workgroups; the largest partial-sum workspace of any pass."""
+    v = [C.c_int() for _ in range(4)]
+    wg, ws = C.c_int64(), C.c_int64()
+    _check(lib().sctl_amd_eval_densities_plan(kernel_id(name), real, nd, Nt, Ns, digits, *[C.byref(x) for x in v], C.byref(wg), C.byref(ws)), "eval_densities_plan")
+    return dict(densities_per_pass=v[0].value, passes=v[1].value, trg_per_lane=v[2].value, src_splits=v[3].value, workgroups=wg.value, workspace_bytes=ws.value)
+
+
 def counters():
     p, f = C.c_int64(), C.c_int64()
     lib().sctl_amd_counters(C.byref(p), C.byref(f))
@@ -264,6 +278,50 @@ def eval_host(name, r_trg, r_src, n_src, v_src, v_trg=None, digits=-1, ctx=None,
         devs = (C.c_int * len(devices))(*devices)
         _check(lib().sctl_amd_eval_host_multi(*args, devs, len(devices)), "eval_host_multi")
     return v_trg
+
+
+def eval_densities_host(name, r_trg, r_src, n_src, V_src, V_trg=None, digits=-1, ctx=None, device=0):
+    """nd densities against one geometry (sctl_amd_eval_densities_host) on numpy arrays: V_src of shape (nd, Ns*SrcDim), returns
+    (nd, Nt*TrgDim).  A V_trg of that shape is accumulated into; None (or another shape) gives a fresh zeroed result."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    if V_src.ndim != 2 or V_src.shape[1] != Ns * info["k0"]:
+        raise SctlAmdError("V_src must have shape (nd, %d)" % (Ns * info["k0"]))
+    nd = V_src.shape[0]
+    if V_trg is None or V_trg.shape != (nd, Nt * info["k1"]):
+        V_trg = np.zeros((nd, Nt * info["k1"]), dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    _check(lib().sctl_amd_eval_densities_host(info["id"], real, nd, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                              _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(V_src, dt, nd * Ns * info["k0"], "V_src"),
+                                              _np_ptr(V_trg, dt, nd * Nt * info["k1"], "V_trg"), digits, cp, cb, device), "eval_densities_host")
+    return V_trg
+
+
+def eval_densities_device(name, r_trg, r_src, n_src, V_src, V_trg=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_densities_device), enqueued on `stream` (default: torch's current stream);
+    V_src of shape (nd, Ns*SrcDim), V_trg (nd, Nt*TrgDim) accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    if V_src.dim() != 2 or V_src.shape[1] != Ns * info["k0"]:
+        raise SctlAmdError("V_src must have shape (nd, %d)" % (Ns * info["k0"]))
+    nd = V_src.shape[0]
+    if V_trg is None or tuple(V_trg.shape) != (nd, Nt * info["k1"]):
+        V_trg = torch.zeros((nd, Nt * info["k1"]), dtype=tdt, device=r_trg.device)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_densities_device(info["id"], real, nd, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                                    _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(V_src, tdt, nd * Ns * info["k0"], "V_src"),
+                                                    _t_ptr(V_trg, tdt, nd * Nt * info["k1"], "V_trg"), digits, cp, cb, C.c_void_p(st.cuda_stream)),
+               "eval_densities_device")
+    return V_trg
 
 
 def _t_ptr(t, torch_dtype, n, what):
@@ -430,6 +488,20 @@ class DirectOp:
         _check(lib().sctl_amd_op_eval(self._h, _np_ptr(v_src, self.dtype, self.Ns * self.info["k0"], "v_src"),
                                       _np_ptr(v_trg, self.dtype, self.Nt * k1, "v_trg"), 1 if accumulate else 0, digits, cp, cb), "op_eval")
         return v_trg
+
+    def eval_densities(self, V_src, V_trg=None, accumulate=False, digits=-1):
+        """eval() for nd densities in one pass (sctl_amd_op_eval_densities): V_src of shape (nd, Ns*SrcDim), returns (nd, Nt*k1) with
+        k1 = TrgDim, or TrgDim/3 with target normals."""
+        k1 = self.info["k1"] // 3 if getattr(self, "_dot", False) else self.info["k1"]
+        if V_src.ndim != 2 or V_src.shape[1] != self.Ns * self.info["k0"]:
+            raise SctlAmdError("V_src must have shape (nd, %d)" % (self.Ns * self.info["k0"]))
+        nd = V_src.shape[0]
+        if V_trg is None or V_trg.shape != (nd, self.Nt * k1):
+            V_trg = np.zeros((nd, self.Nt * k1), dtype=self.dtype)
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_densities(self._h, nd, _np_ptr(V_src, self.dtype, nd * self.Ns * self.info["k0"], "V_src"),
+                                                _np_ptr(V_trg, self.dtype, nd * self.Nt * k1, "V_trg"), 1 if accumulate else 0, digits, cp, cb), "op_eval_densities")
+        return V_trg
 
     def set_near(self, trg_dim, elem_nds_cnt, near_elem_cnt, K_near, near_scatter_index, near_trg_cnt, near_trg_dsp, K_near_cnt=None):
         """Attach the near-field operator of the same BoundaryIntegralOp (the arrays of NearOp) for the current targets."""

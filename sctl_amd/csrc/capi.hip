@@ -1,6 +1,7 @@
 // C ABI of libsctl_amd.so (include/sctl_amd.h): argument checks, launch planning, host<->device staging
-// and the one-process multi-GPU driver.  All arithmetic lives in eval_kernel.hpp / ukernels.hpp.
+// and the one-process multi-GPU driver.  All arithmetic lives in eval_kernel.hpp / multi_kernel.hpp / ukernels.hpp.
 #include "internal.hpp"
+#include "multi_kernel.hpp"
 #include "workspace.hpp"
 
 #include <dlfcn.h>
@@ -470,6 +471,124 @@ hipError_t grow(void** p, size_t* cap, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);
   if (e == hipSuccess) *cap = bytes;
   return e;
+}
+
+// ---- several densities against one geometry (sctl_amd_eval_densities_*, multi_kernel.hpp) ----------------------------------------------
+// Launch table of the multi-density forms: the built-in kernels only; a registered plugin kernel has none (null) and is evaluated one density at a time.
+const MultiEntry* multi_entry(int kernel_id) {
+  static const MultiEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &multi_Laplace3D_FxU(), &multi_Laplace3D_DxU(), &multi_Laplace3D_FxdU(),  &multi_Stokes3D_FxU(),      &multi_Stokes3D_DxU(),
+      &multi_Stokes3D_FxT(),  &multi_Stokes3D_FSxU(), &multi_Stokes3D_FxUP(), &multi_Laplace3D_FDxUdU(), &multi_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+// the form for `left` densities still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
+int multi_form(const MultiEntry& me, int left) {
+  for (int i = 0; i < kNumMultiM; i++)
+    if (me.t[i] && (kMultiM[i] >= left || kMultiM[i] == me.m_max)) return i;
+  return 0;
+}
+constexpr int64_t kMultiWorkspaceCap = (int64_t)2 << 30;   // partial sums of one launch, [M][splits][Nt*K1]
+
+struct MultiPlan {
+  int form, M, T, splits;
+  int64_t chunk, nt_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the targets of one launch of nt_launch targets
+};
+// make_plan with M densities per source: the same workgroup target, the L2 rule counting all M densities in a split's source bytes, and the
+// splits always in eights from 8 on (the XCD-owned mapping).  Partial sums [M][splits][nt*K1] stay within 2 GB by cutting the targets into
+// several launches, never by dropping below the L2 rule's split count.
+MultiPlan make_plan_multi(const KernelEntry& k, const MultiEntry& me, int form, int real, int64_t Nt, int64_t Ns) {
+  MultiPlan p{};
+  p.form = form; p.M = kMultiM[form]; p.T = me.t[form];
+  const int64_t rs = (real == SCTL_AMD_F64 ? 8 : 4), per_wg = (int64_t)kBlock * p.T;
+  const int64_t ntile = (Ns + kTile - 1) / kTile;
+  int64_t l2 = 1;
+  if ((double)Nt * (double)Ns >= 17179869184.0) {
+    const int64_t src_bytes = Ns * (3 + k.nd + (int64_t)p.M * k.k0) * rs;
+    l2 = (src_bytes + (2 << 20) - 1) / (2 << 20);
+    l2 = (l2 + 7) / 8 * 8;
+    if (l2 > 64) l2 = 64;
+  }
+  auto geometry = [&](int64_t nt) {
+    p.nt_launch = nt;
+    p.wg_x = (nt + per_wg - 1) / per_wg;
+    const int64_t want = (int64_t)cu_count() * ((double)nt * (double)Ns < 2147483648.0 ? 4 : 8);
+    int64_t s = (want + p.wg_x - 1) / p.wg_x;
+    if (s > 1024) s = 1024;
+    if (s < l2) s = l2;
+    if (s > ntile) s = ntile;
+    if (s < 1) s = 1;
+    const int64_t tiles_per = (ntile + s - 1) / s;
+    p.chunk = (tiles_per > 0 ? tiles_per : 1) * kTile;
+    int64_t splits = (Ns + p.chunk - 1) / p.chunk;
+    if (splits >= 8) splits = (splits + 7) / 8 * 8;   // (the splits past the sources have no work)
+    p.splits = (int)(splits < 1 ? 1 : splits);
+    p.workspace_bytes = p.splits > 1 ? (int64_t)p.M * p.splits * nt * k.k1 * rs : 0;
+  };
+  p.launches = 1;
+  for (;;) {
+    int64_t nt = (Nt + p.launches - 1) / p.launches;
+    nt = (nt + per_wg - 1) / per_wg * per_wg;
+    if (nt > Nt) nt = Nt;
+    geometry(nt);
+    if (p.workspace_bytes <= kMultiWorkspaceCap || nt <= per_wg) break;
+    const int64_t more = (p.workspace_bytes + kMultiWorkspaceCap - 1) / kMultiWorkspaceCap * p.launches;   // (at least one more launch)
+    p.launches = more > p.launches ? more : p.launches + 1;
+  }
+  p.launches = (Nt + p.nt_launch - 1) / p.nt_launch;
+  return p;
+}
+
+// nd >= 2 densities, density-major, on the device: passes of the widest form, the last pass on the narrowest form that takes what is left (a
+// single density left over runs on the 2-density form, so that every pass keeps this planner's 2 GB bound).  v is accumulated into.
+// A plugin kernel has no multi-density form: its densities go one at a time through the single-density path.
+template <class R>
+int eval_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits,
+                            const void* ctx, hipStream_t st, int64_t nt_whole = 0, bool presorted = false) {
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  const int64_t f_stride = Ns * k.k0, v_stride = Nt * k.k1;
+  const MultiEntry* me = multi_entry(k.id);
+  const int mode = mode_for(real, digits);
+  for (int m0 = 0; m0 < nd;) {
+    const int left = nd - m0;
+    if (!me) {
+      const int rc = eval_device_t<R>(k, real, Nt, Ns, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride, digits, ctx, st, nt_whole, presorted);
+      if (rc) return rc;
+      m0++;
+      continue;
+    }
+    (void)hipGetLastError();
+    const MultiPlan p = make_plan_multi(k, *me, multi_form(*me, left), real, Nt, Ns);
+    const int nact = left < p.M ? left : p.M;
+    MultiArgs<R> a{};
+    a.Ns = Ns; a.xs = xs; a.xn = xn; a.f = f + m0 * f_stride; a.f_stride = f_stride; a.v_stride = v_stride;
+    a.chunk = p.chunk; a.nact = nact; a.scale = (R)(k.scale / k.acc_factor[mode]); a.ctx = make_ctx(k, ctx);
+    if (p.splits > 1) {
+      void* ws = nullptr;
+      HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+      a.partial = (R*)ws;
+    }
+    MultiLaunch<R> launch;
+    if constexpr (std::is_same<R, double>::value) launch = me->f64[mode][p.form];
+    else launch = me->f32[mode][p.form];
+    for (int64_t t0 = 0; t0 < Nt; t0 += p.nt_launch) {
+      const int64_t nt = (Nt - t0 < p.nt_launch) ? Nt - t0 : p.nt_launch;
+      a.Nt = nt; a.xt = xt + t0 * 3; a.v_trg = v + m0 * v_stride + t0 * k.k1;
+      const dim3 grid((unsigned)((nt + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T)), (unsigned)p.splits);
+      launch(a, grid, st);
+      HIP_TRY(hipGetLastError());
+      if (p.splits > 1) {
+        const int64_t n = nt * k.k1;
+        for (int m = 0; m < nact; m++)
+          hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.v_trg + m * v_stride,
+                             (const R*)(a.partial + (int64_t)m * p.splits * n), n, p.splits, a.scale);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    g_pairs += (int64_t)nact * Nt * Ns;
+    g_flops += (int64_t)nact * Nt * Ns * k.flops;
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
 }
 }  // namespace
 }  // namespace sctl_amd
@@ -1256,6 +1375,197 @@ int sctl_amd_op_set_near(sctl_amd_op* op, int src_dim, int trg_dim, int64_t Nele
     }
     if (rc != SCTL_AMD_OK) { const std::string msg = g_err; op_release_near(op); g_err = msg; return rc; }
   }
+  return SCTL_AMD_OK;
+}
+
+// ---- several densities against one geometry ----------------------------------------------------------------------------------------------
+// nd == 1 goes through the single-density entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+static int check_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                           const void* v_src, const void* v_trg, int ctx_bytes, const void* ctx) {
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd > 0 && ((Ns > 0 && !v_src) || (Nt > 0 && !v_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                   const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, v_src, v_trg, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_device(kernel, real, Nt, Ns, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes, stream);
+  if (device_count_quiet() <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (real == SCTL_AMD_F64)
+    return eval_densities_device_t<double>(*k, real, nd, Nt, Ns, (const double*)r_trg, (const double*)r_src, (const double*)n_src, (const double*)v_src,
+                                           (double*)v_trg, digits, ctx, (hipStream_t)stream);
+  return eval_densities_device_t<float>(*k, real, nd, Nt, Ns, (const float*)r_trg, (const float*)r_src, (const float*)n_src, (const float*)v_src, (float*)v_trg,
+                                        digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                 const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, v_src, v_trg, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_host(kernel, real, Nt, Ns, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes, device);
+  const int avail = device_count_quiet();
+  if (avail <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (device < 0 || device >= avail) return fail(SCTL_AMD_ERR_NO_DEVICE, "device index out of range");
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  const size_t rs = (real == SCTL_AMD_F64) ? 8 : 4;
+  DeviceScope dev_scope(device);
+  HIP_TRY(dev_scope.err);
+  // the calling thread's slot for this device, as the single-density host entry uses it
+  HostSlot& hs = host_slot(device);
+  if (!hs.st.s) HIP_TRY(hipStreamCreateWithFlags(&hs.st.s, hipStreamNonBlocking));
+  hipStream_t st = hs.st.s;
+  struct Release { HostSlot& h; ~Release() { h.trim((size_t)64 << 20); } } release{hs};
+  const size_t b_xt = (size_t)Nt * 3 * rs, b_xs = (size_t)Ns * 3 * rs, b_xn = (size_t)Ns * k->nd * rs, b_f = (size_t)nd * Ns * k->k0 * rs,
+               b_v = (size_t)nd * Nt * k->k1 * rs;
+  HIP_TRY(hs.buf[0].reserve(b_xt));
+  HIP_TRY(hs.buf[1].reserve(b_xs));
+  HIP_TRY(hs.buf[2].reserve(b_xn));
+  HIP_TRY(hs.buf[3].reserve(b_f));
+  HIP_TRY(hs.buf[4].reserve(b_v));
+  HIP_TRY(hs.stage.reserve(pad256(b_xt) + pad256(b_xs) + pad256(b_xn) + pad256(b_f) + pad256(b_v)));
+  HIP_TRY(upload(hs.buf[0].p, r_trg, b_xt, hs.stage, st));
+  HIP_TRY(upload(hs.buf[1].p, r_src, b_xs, hs.stage, st));
+  if (k->nd) HIP_TRY(upload(hs.buf[2].p, n_src, b_xn, hs.stage, st));
+  HIP_TRY(upload(hs.buf[3].p, v_src, b_f, hs.stage, st));
+  HIP_TRY(hipMemsetAsync(hs.buf[4].p, 0, b_v, st));
+  if (real == SCTL_AMD_F64)
+    rc = eval_densities_device_t<double>(*k, real, nd, Nt, Ns, (const double*)hs.buf[0].p, (const double*)hs.buf[1].p, (const double*)hs.buf[2].p,
+                                         (const double*)hs.buf[3].p, (double*)hs.buf[4].p, digits, ctx, st);
+  else
+    rc = eval_densities_device_t<float>(*k, real, nd, Nt, Ns, (const float*)hs.buf[0].p, (const float*)hs.buf[1].p, (const float*)hs.buf[2].p,
+                                        (const float*)hs.buf[3].p, (float*)hs.buf[4].p, digits, ctx, st);
+  if (rc) return rc;
+  char* out = hs.stage.take(b_v);
+  HIP_TRY(hipMemcpyAsync(out, hs.buf[4].p, b_v, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t n = (int64_t)nd * Nt * k->k1;
+  if (real == SCTL_AMD_F64) { double* o = (double*)v_trg; const double* s = (const double*)out; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  else { float* o = (float*)v_trg; const float* s = (const float*)out; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void* v_trg, int accumulate, int digits, const void* ctx, int ctx_bytes) {
+  if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  const KernelEntry& k = *op->k;
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return fail(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (nd > 0 && ((op->Ns > 0 && !v_src) || (op->Nt > 0 && !v_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
+  if (nd == 0) return SCTL_AMD_OK;
+  if (nd == 1) return sctl_amd_op_eval(op, v_src, v_trg, accumulate, digits, ctx, ctx_bytes);
+  const size_t rs = (op->real == SCTL_AMD_F64) ? 8 : 4;
+  const int64_t Ns = op->Ns, Nt = op->Nt;
+  const int k1 = op->have_trg_normals ? k.k1 / 3 : k.k1;   // components per target that go back to the host
+  return op_for_each_device(op, [&](OpDevice& d) -> int {
+    const int64_t nt = d.t1 - d.t0;
+    if (nt == 0) return SCTL_AMD_OK;
+    DeviceScope dev_scope(d.device);
+    HIP_TRY(dev_scope.err);
+    const size_t fbytes = (size_t)nd * Ns * k.k0 * rs, vbytes = (size_t)nd * nt * k.k1 * rs, obytes = (size_t)nd * nt * k1 * rs;
+    HIP_TRY(grow(&d.f, &d.cap_f, fbytes));
+    HIP_TRY(grow(&d.v, &d.cap_v, vbytes));
+    HIP_TRY(d.stage.reserve(pad256(fbytes) + pad256(obytes)));
+    HIP_TRY(upload(d.f, v_src, fbytes, d.stage, d.st));
+    const unsigned nbf = (unsigned)((Ns * k.k0 + kBlock - 1) / kBlock), nbo = (unsigned)((nt * k1 + kBlock - 1) / kBlock);
+    if (op->have_weights && Ns > 0) {   // every density x the quadrature weights
+      for (int m = 0; m < nd; m++) {
+        if (op->real == SCTL_AMD_F64) hipLaunchKernelGGL((scale_density_kernel<double>), dim3(nbf), dim3(kBlock), 0, d.st, (double*)d.f + (int64_t)m * Ns * k.k0, (const double*)d.w, Ns, k.k0);
+        else hipLaunchKernelGGL((scale_density_kernel<float>), dim3(nbf), dim3(kBlock), 0, d.st, (float*)d.f + (int64_t)m * Ns * k.k0, (const float*)d.w, Ns, k.k0);
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(d.v, 0, vbytes, d.st));
+    int rc = SCTL_AMD_OK;
+    const int64_t nt_whole = op->perm.empty() ? 0 : Nt;
+    if (Ns == 0) {}
+    else if (op->real == SCTL_AMD_F64)
+      rc = eval_densities_device_t<double>(k, op->real, nd, nt, Ns, (const double*)d.xt, (const double*)d.xs, (const double*)d.xn, (const double*)d.f, (double*)d.v,
+                                           digits, ctx, d.st, nt_whole, !op->perm.empty());
+    else
+      rc = eval_densities_device_t<float>(k, op->real, nd, nt, Ns, (const float*)d.xt, (const float*)d.xs, (const float*)d.xn, (const float*)d.f, (float*)d.v,
+                                          digits, ctx, d.st, nt_whole, !op->perm.empty());
+    if (rc) return rc;
+    void* result = d.v;
+    if (op->have_trg_normals) {   // contract each density's potential with the target normals
+      HIP_TRY(grow(&d.u, &d.cap_u, obytes));
+      for (int m = 0; m < nd; m++) {
+        if (op->real == SCTL_AMD_F64)
+          hipLaunchKernelGGL((normal_dot_kernel<double>), dim3(nbo), dim3(kBlock), 0, d.st, (const double*)d.v + (int64_t)m * nt * k.k1, (const double*)d.nt,
+                             (double*)d.u + (int64_t)m * nt * k1, nt, k1);
+        else
+          hipLaunchKernelGGL((normal_dot_kernel<float>), dim3(nbo), dim3(kBlock), 0, d.st, (const float*)d.v + (int64_t)m * nt * k.k1, (const float*)d.nt,
+                             (float*)d.u + (int64_t)m * nt * k1, nt, k1);
+      }
+      HIP_TRY(hipGetLastError());
+      result = d.u;
+    }
+    const char* out = d.stage.take(obytes);
+    HIP_TRY(hipMemcpyAsync((void*)out, result, obytes, hipMemcpyDeviceToHost, d.st));
+    HIP_TRY(hipStreamSynchronize(d.st));
+    // this slab of every density row, into the caller's target order (Morton slab -> perm when the targets are kept sorted)
+    const int64_t* perm = op->perm.empty() ? nullptr : op->perm.data() + d.t0;
+    auto scatter = [&](auto* o, const auto* sv) {
+      for (int m = 0; m < nd; m++) {
+        auto* orow = o + (int64_t)m * Nt * k1;
+        const auto* srow = sv + (int64_t)m * nt * k1;
+        for (int64_t i = 0; i < nt; i++) {
+          const int64_t t = perm ? perm[i] : d.t0 + i;
+          for (int c = 0; c < k1; c++) {
+            auto& e = orow[t * k1 + c];
+            e = (accumulate ? e : 0) + srow[i * k1 + c];
+          }
+        }
+      }
+    };
+    if (op->real == SCTL_AMD_F64) scatter((double*)v_trg, (const double*)out);
+    else scatter((float*)v_trg, (const float*)out);
+    return SCTL_AMD_OK;
+  });
+}
+
+int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* densities_per_pass, int* passes, int* trg_per_lane,
+                                 int* src_splits, int64_t* workgroups, int64_t* workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (!k) return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
+  if (real != SCTL_AMD_F64 && real != SCTL_AMD_F32) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "real must be SCTL_AMD_F64 or SCTL_AMD_F32");
+  if (Nt < 0 || Ns < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative size");
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  int dpp = 0, np = 0, t = 0, s = 0;
+  int64_t wg = 0, ws = 0;
+  const MultiEntry* me = multi_entry(k->id);
+  if (nd == 1 || (nd > 1 && !me)) {   // the single-density plan, once per density
+    const int rc = sctl_amd_eval_plan(kernel, real, Nt, Ns, Nt, digits, &t, &s, &wg, &ws);
+    if (rc) return rc;
+    dpp = 1; np = nd;
+  } else if (nd > 1) {
+    // the first pass is the widest; the workspace is the largest any pass asks for
+    for (int m0 = 0; m0 < nd;) {
+      const int left = nd - m0;
+      const MultiPlan p = make_plan_multi(*k, *me, multi_form(*me, left), real, Nt > 0 ? Nt : 1, Ns);
+      if (np == 0) {
+        dpp = p.M; t = p.T; s = p.splits;
+        for (int64_t t0 = 0; t0 < Nt; t0 += p.nt_launch) {   // workgroups of all target launches of the pass
+          const int64_t n = (Nt - t0 < p.nt_launch) ? Nt - t0 : p.nt_launch;
+          wg += (n + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T) * p.splits;
+        }
+      }
+      ws = p.workspace_bytes > ws ? p.workspace_bytes : ws;
+      np++;
+      m0 += left < p.M ? left : p.M;
+    }
+  }
+  if (densities_per_pass) *densities_per_pass = dpp;
+  if (passes) *passes = np;
+  if (trg_per_lane) *trg_per_lane = t;
+  if (src_splits) *src_splits = s;
+  if (workgroups) *workgroups = wg;
+  if (workspace_bytes) *workspace_bytes = ws;
   return SCTL_AMD_OK;
 }
 
