@@ -240,10 +240,18 @@ template <class R> __device__ __forceinline__ R dot3(const R (&d)[3], const R* v
 // a factor 1 + 3/4 d_max^2 — would put the worst case at +-2.1e-15 but move the mean to +1.9e-15: rms 1.9e-15 against 3.0e-16.)
 constexpr double kNewton2MeanErr = -1.725e-16;
 constexpr double newton2_factor(int p) { return (p == 1 ? 2.0 : p == 3 ? 8.0 : 32.0) * (1.0 + p * kNewton2MeanErr); }
-template <bool MASKED, class R> __device__ __forceinline__ R rsqrt_newton2(R r2, const RsqConst<R>& K) {
+// The refinements below come in two forms: the product y0 P itself, and the two factors {y0, P} (rsqrt_scaled_split) for a caller that fuses
+// the product into its accumulate, acc = fma(y0, P, acc) — the folded far pair of the tile-centred single layer (centered_kernel.hpp), whose
+// source record carries the density inside y0.
+template <class R> struct RsqSplit { R y, p; };
+template <bool MASKED, class R> __device__ __forceinline__ RsqSplit<R> rsqrt_newton2_split(R r2, const RsqConst<R>& K) {
   const R y = rsqrt_masked<0, MASKED>(r2, K);
   const R a = r2 * y;
-  return y * fma_(-a, y, R(3));
+  return {y, fma_(-a, y, R(3))};
+}
+template <bool MASKED, class R> __device__ __forceinline__ R rsqrt_newton2(R r2, const RsqConst<R>& K) {
+  const RsqSplit<R> s = rsqrt_newton2_split<MASKED>(r2, K);
+  return s.y * s.p;
 }
 
 // MODE 2 (full precision, the default) for the same kernels: the CUBIC step without its normalisation, in FOUR instructions.
@@ -260,10 +268,14 @@ template <bool MASKED, class R> __device__ __forceinline__ R rsqrt_newton2(R r2,
 // own default approx_rsqrt (2.5 ulp) rather than Halley's 1.25 ulp, with a smaller rms than the reference's.
 // With the masked seed y0 = 0 the result is 0; an unmasked coincident pair gives z = 0 * inf = NaN, which the speculative pass detects.
 constexpr double cubic83_factor(int p) { return p == 1 ? 0x1.5555550000000p+1 : p == 3 ? 0x1.2f684af684bdep+4 : 0x1.0db20937d5dcdp+7; }
-template <bool MASKED> __device__ __forceinline__ double rsqrt_cubic83(double r2, const RsqConst<double>& K) {
+template <bool MASKED> __device__ __forceinline__ RsqSplit<double> rsqrt_cubic83_split(double r2, const RsqConst<double>& K) {
   const double y = rsqrt_masked<0, MASKED>(r2, K);
   const double z = __builtin_fma(r2, y * y, -K.c53);
-  return y * __builtin_fma(z, z, K.k209);
+  return {y, __builtin_fma(z, z, K.k209)};
+}
+template <bool MASKED> __device__ __forceinline__ double rsqrt_cubic83(double r2, const RsqConst<double>& K) {
+  const RsqSplit<double> s = rsqrt_cubic83_split<MASKED>(r2, K);
+  return s.y * s.p;
 }
 // fp32 never runs MODE 2 (capi.hip: mode_for); kept consistent with the shared scale factor
 template <bool MASKED> __device__ __forceinline__ float rsqrt_cubic83(float r2, const RsqConst<float>& K) { return rsqrt_masked<1, MASKED>(r2, K) * (float)cubic83_factor(1); }
@@ -273,6 +285,13 @@ template <int MODE, bool MASKED, class R> __device__ __forceinline__ R rsqrt_sca
   if constexpr (MODE == 1) return rsqrt_newton2<MASKED>(r2, K);
   else if constexpr (MODE == 2) return rsqrt_cubic83<MASKED>(r2, K);
   else return rsqrt_masked<0, MASKED>(r2, K);
+}
+// ... as the factors {y0, P} with y0 P = rsqrt_scaled<MODE> (fp64; MODE 0: P = 1).  Both refinements depend on r2 only through w = r2 y0^2, so they
+// are scale-invariant: for r2 = k r^2 the seed is y0 = 1 / (sqrt(k) r) and y0 P is the mode's C / r times 1 / sqrt(k), with the same relative error.
+template <int MODE, bool MASKED> __device__ __forceinline__ RsqSplit<double> rsqrt_scaled_split(double r2, const RsqConst<double>& K) {
+  if constexpr (MODE == 1) return rsqrt_newton2_split<MASKED>(r2, K);
+  else if constexpr (MODE == 2) return rsqrt_cubic83_split<MASKED>(r2, K);
+  else return {rsqrt_masked<0, MASKED>(r2, K), 1.0};
 }
 constexpr double rsqrt_scaled_factor(int mode, int p) { return mode == 1 ? newton2_factor(p) : mode == 2 ? cubic83_factor(p) : 1; }
 // r^-3 and r^-5 for the kernels that need only that power (double layer, gradient, stresslet, traction).  MODE 2 does not cube the refined 1/r:

@@ -19,8 +19,8 @@ namespace sctl_amd {
   } while (0)
 
 // Targets per lane of the vector-pipe kernel (centered_kernel.hpp): 64 T Morton-consecutive targets share a centre and every staged tile.  fp64 single and double
-// layer: FOUR — half the per-tile staging and LDS reads per pair for a somewhat larger cluster; the full-precision kernel still fits four waves per SIMD (125
-// registers), the others three.  A/B on one box (profiles/r03_ab_centered_T.txt; T = 2 -> 4 -> 8): Laplace SL 2^20 x 2^20 405.4 -> 397.7 -> 405.9 ms at full
+// layer: FOUR — half the per-tile staging and LDS reads per pair for a somewhat larger cluster; the full-precision kernel still fits four waves per SIMD (126
+// registers with the folded far records), the others three.  A/B on one box (profiles/r03_ab_centered_T.txt; T = 2 -> 4 -> 8): Laplace SL 2^20 x 2^20 405.4 -> 397.7 -> 405.9 ms at full
 // precision, 383.6 -> 369.5 -> 379.4 ms at 10 digits; double layer 563.9 -> 542.5 -> 534.1 ms.  fp32 keeps two: its far pairs are written as ONE packed stream over
 // exactly two targets, and its default accuracy runs on the matrix cores anyway.  The gradient kernel (round 4) takes three.  Each policy says so itself (targets_per_lane).
 

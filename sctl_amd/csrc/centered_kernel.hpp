@@ -152,14 +152,46 @@ template <class R> struct CenteredFxU {      // u += f / r
     if (DUP) { base[2 * q] = e.f; base[2 * q + 1] = e.f2; }
     else base[q] = e.f;
   }
+  // fp64 FOLDS the density into the far record.  With k = 1 / f^2 the record is {k x', k y', k z', k |x_s'|^2} and the extra real is k, so that
+  //     r2' = fma(|x_t'|^2, k, k |x_s'|^2) + (-2 x_t').(k x_s') = k r^2        (the same four instructions as the distance without k)
+  // and the seed rsq(r2') = |f| / r.  The refinement is scale-invariant (rsqrt_scaled_split), so y0 P = C |f| / r and the pair ends in
+  // acc = fma(+-y0, P, acc): the product by the density and the refinement's last product are one instruction — 8 fp64 instructions + v_rsq_f64
+  // per far pair at full precision where the unfolded pair takes 9 + v_rsq_f64.  The sign of f is not in the record: the kernel keeps the far
+  // sources of either sign in a list of their own (FOLD) and subtracts the negative ones (the FMA's neg modifier).  Sources the fold cannot take
+  // go elsewhere (fold_class).
+  static constexpr bool FOLD = !DUP;
+  // 1: positive far list, -1: negative far list, 0: f == 0, contributes exactly 0 (dropped), 2: the exact pair — f not finite (NaN and inf propagate
+  // as in the reference), or a scaled record out of the safe range: the terms of r2' are at most ~2.5 k |x_s'|^2 (a far source has r^2 >= |x_s'|^2 / 4),
+  // and |k x_s'| = k |x_s'|^2 / |x_s'| <= 2^750 with the two bands below
+  static __device__ __forceinline__ int fold_class(R f, R ss, R& k) {
+    if (f == R(0)) return 0;
+    k = R(1) / (f * f);   // f * f over- or underflows to inf or 0 for |f| beyond ~1e+-154: k ss is then 0 or inf, out of the band
+    const R kss = k * ss;
+    if (!(kss >= R(0x1p-600) && kss <= R(0x1p600) && ss >= R(0x1p-300) && ss <= R(0x1p300))) return 2;
+    return f > R(0) ? 1 : -1;
+  }
+  static __device__ __forceinline__ void put_folded(typename Rec4<R>::V* rec, R* base, int q, const R (&p)[3], R ss, R k) {
+    Rec4<R>::put(rec + q * Rec4<R>::NW, k * p[0], k * p[1], k * p[2], k * ss);
+    base[q] = k;
+  }
   template <int MODE> static __device__ __forceinline__ void far_pair(R& acc, const R (&m2x)[3], R tt, const R (&b)[4], const Extra& e, const RsqConst<R>& K) {
     const R r2 = fma_(m2x[0], b[0], fma_(m2x[1], b[1], fma_(m2x[2], b[2], tt + b[3])));
     acc = fma_(e.f, rsqrt_scaled<MODE, false>(r2, K), acc);   // MODE 1: 2/r, MODE 2: (8/3)/r, as Ker::pair (acc_factor)
   }
+  // a folded far pair (e.f = k); NEG: a source of the negative list
+  template <int MODE, bool NEG> static __device__ __forceinline__ void far_pair_folded(R& acc, const R (&m2x)[3], R tt, const R (&b)[4], const Extra& e,
+                                                                                       const RsqConst<R>& K) {
+    const R r2 = fma_(m2x[0], b[0], fma_(m2x[1], b[1], fma_(m2x[2], b[2], fma_(tt, e.f, b[3]))));
+    const RsqSplit<R> s = rsqrt_scaled_split<MODE, false>(r2, K);   // y0 P = C |f| / r, as Ker::pair (acc_factor)
+    acc = fma_(NEG ? -s.y : s.y, s.p, acc);
+  }
   // all T targets of the lane against one far source
-  template <int MODE, int T, class KC> static __device__ __forceinline__ void far_pairs(R (&acc)[T][NF], const FarTargets<R, T>& tg, const R (&b)[4], const Extra& e,
-                                                                                          const KC& K) {
-    if constexpr (std::is_same<R, float>::value && T == 2) {
+  template <int MODE, int T, bool NEG = false, class KC> static __device__ __forceinline__ void far_pairs(R (&acc)[T][NF], const FarTargets<R, T>& tg, const R (&b)[4],
+                                                                                                          const Extra& e, const KC& K) {
+    if constexpr (FOLD) {
+#pragma unroll
+      for (int j = 0; j < T; j++) far_pair_folded<MODE, NEG>(acc[j][0], tg.m2x[j], tg.tt[j], b, e, K.rsq);
+    } else if constexpr (std::is_same<R, float>::value && T == 2) {
       f32x2 r2 = pk_add_hi(tg.tp, f32x2{b[2], b[3]});
       r2 = tg.mp[2] * f32x2{b[2], b[2]} + r2;
       r2 = tg.mp[1] * f32x2{b[1], b[1]} + r2;
@@ -331,6 +363,10 @@ __device__ __forceinline__ void centered_tile_and_split(unsigned& tile_idx, unsi
     split_idx = xcd * per + j / gridDim.x;
   }
 }
+// whether a policy folds the density into its far records (CenteredFxU<double>::FOLD): two far lists by the sign of the density
+template <class CP, class = void> struct FoldsDensity : std::false_type {};
+template <class CP> struct FoldsDensity<CP, std::void_t<decltype(CP::FOLD)>> : std::integral_constant<bool, CP::FOLD> {};
+
 // a.xt: Morton-sorted targets; a.v_trg / a.partial: indexed like a.xt (the caller scatters back).
 // (asking the compiler for 5-6 waves/SIMD instead of the 4 its registers allow, or unrolling the far loop by 2 or 8 instead of 4, costs 0-3 %:
 // profiles/r03_ab_centered_occupancy.txt)
@@ -344,8 +380,11 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
   constexpr int kNearCap = CP::NEAR_CAP < sctl_amd::kNearCap ? CP::NEAR_CAP : sctl_amd::kNearCap;
   constexpr int NEARW = (Ker::NREC + 3) / 4;                  // Rec4 groups of a near record (the kernel's packed exact record)
   constexpr int XV = (CP::XW * (int)sizeof(R) + 15) / 16;     // 16-byte words of the extra far record
-  __shared__ V farB[(kWaveTile + UNR) * NW];                  // {x', y', z', |x_s'|^2}   (+ the leftovers of earlier tiles)
-  __shared__ V farXv[(kWaveTile + UNR) * (XV > 0 ? XV : 1)];    // the policy's extra far reals (density, or the normal terms)
+  constexpr bool FOLD = FoldsDensity<CP>::value;
+  // far records: one list, or (FOLD) the positive list from the front and the negative one from the back, each with its own leftovers (< UNR)
+  constexpr int FAR_CAP = FOLD ? kWaveTile + 2 * (UNR - 1) : kWaveTile + UNR;
+  __shared__ V farB[FAR_CAP * NW];                            // {x', y', z', |x_s'|^2}   (+ the leftovers of earlier tiles)
+  __shared__ V farXv[FAR_CAP * (XV > 0 ? XV : 1)];              // the policy's extra far reals (density, or the normal terms)
   __shared__ V nearA[(kNearCap + 2) * NW * NEARW];            // packed exact records; near sources are collected over
                                                               // several tiles and evaluated in batches, so the exact loop runs
                                                               // rarely and with a long trip count
@@ -537,8 +576,109 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
 
   // The far list is consumed UNR records at a time.  fp64: what is left over (< UNR) moves to the front of the list for the next tile instead
   // of being padded with null sources (1.5 evaluations in ~62 per tile): +0.9 % (A/B, profiles/r02_ab_far_carry.txt).  fp32, whose tile
-  // costs a third of the cycles, gains nothing from it and pads every tile.
-  if constexpr (sizeof(R) == 8) {
+  // costs a third of the cycles, gains nothing from it and pads every tile.  A policy that folds the density into its far records (FOLD) keeps
+  // two such lists, one per sign, each with its own leftovers; no folded record contributes exactly 0, so the last leftovers are not padded.
+  if constexpr (FOLD) {
+    static_assert(SCALAR && NF == 1, "the fold is the single layer's");
+    // stage_tile with the far sources split by the sign of the density into the positive list (records [0, n+) of farB / farX, leftovers
+    // of earlier tiles first) and the negative list (records FAR_CAP - 1 - i, i in [0, n-)).  Sets the numbers of new far sources of either sign.
+    // The two lists never meet: n+ + n- <= 64 + 2 (UNR - 1) = FAR_CAP.
+    auto stage_tile_folded = [&](int it, int cpos, int cneg, int& npos, int& nneg) {
+      const int ns = (it == ntile - 1) ? (int)(len - (int64_t)it * kWaveTile) : kWaveTile;
+      const bool valid = lane < ns;
+      const R p[3] = {x[0] - c[0], x[1] - c[1], x[2] - c[2]};
+      const R ss = len2(p);
+      const bool far = valid && (ss > near_r2);
+      R k = 0;
+      const int cls = far ? CP::fold_class(f[0], ss, k) : 2;
+      const bool is_pos = far && cls == 1, is_neg = far && cls == -1, is_near = valid && cls == 2;
+      const unsigned long long bp = __ballot(is_pos), bq = __ballot(is_neg), bn = __ballot(is_near);
+      const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+      const int nnear = __popcll(bn);
+      __syncthreads();   // previous tile's far records fully consumed
+      if (nn + nnear > kNearCap) {   // wave-uniform: evaluate the pending near sources before the list overflows
+        flush_near();
+        __syncthreads();
+      }
+      if (is_pos) CP::put_folded(farB, farX, cpos + __popcll(bp & below), p, ss, k);
+      else if (is_neg) CP::put_folded(farB, farX, FAR_CAP - 1 - (cneg + __popcll(bq & below)), p, ss, k);
+      else if (is_near) put_near(nn + __popcll(bn & below), x, nrm, f);
+      nn += nnear;
+      npos = __popcll(bp);
+      nneg = __popcll(bq);
+    };
+    // one far record into tacc; NEG: record i of the negative list, subtracted
+    auto far_folded = [&](R (&tacc)[T][NF], int i, auto neg) {
+      constexpr bool NEG = decltype(neg)::value;
+      const int q = NEG ? FAR_CAP - 1 - i : i;
+      R b[4];
+      Rec4<R>::get(farB + q * NW, b);
+      const typename CP::Extra e = CP::load_extra(farX, q);
+      CP::template far_pairs<MODE, T, NEG>(tacc, tg, b, e, K);
+    };
+    // records [0, mp) of the positive and [0, mn) of the negative list (multiples of UNR).  Groups of UNR from either list alternate into the same
+    // partial sums while both last, so that the positive and negative terms cancel as they come (summing either sign apart and taking the difference at the
+    // end loses digits to the cancellation)
+    auto run_far_folded = [&](int mp, int mn) {
+      R tacc[T][NF];
+#pragma unroll
+      for (int j = 0; j < T; j++) tacc[j][0] = 0;
+      const std::integral_constant<bool, false> pos;
+      const std::integral_constant<bool, true> neg;
+      const int mb = mp < mn ? mp : mn;
+      int s = 0;
+      for (; s < mb; s += UNR) {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) far_folded(tacc, s + u, pos);
+#pragma unroll
+        for (int u = 0; u < UNR; u++) far_folded(tacc, s + u, neg);
+      }
+      for (; s < mp; s += UNR) {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) far_folded(tacc, s + u, pos);
+      }
+      for (; s < mn; s += UNR) {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) far_folded(tacc, s + u, neg);
+      }
+#pragma unroll
+      for (int j = 0; j < T; j++) acc[j][0] += tacc[j][0];
+    };
+    int cpos = 0, cneg = 0;   // leftovers of either list from the previous tiles (wave-uniform, < UNR each)
+    for (int it = 0; it < ntile; it++) {
+      int npos, nneg;
+      stage_tile_folded(it, cpos, cneg, npos, nneg);
+      const int np = cpos + npos, nq = cneg + nneg, mp = np & ~(UNR - 1), mq = nq & ~(UNR - 1);
+      if (it + 1 < ntile) load_source(it + 1);
+      __syncthreads();
+      run_far_folded(mp, mq);
+      cpos = np - mp;
+      cneg = nq - mq;
+      // the leftovers to the front of their list (one wave: its LDS operations complete in program order; the lists do not overlap): lanes [0, cpos)
+      // move the positive ones, lanes [32, 32 + cneg) the negative ones
+      const bool mv_pos = mp > 0 && lane < cpos, mv_neg = mq > 0 && lane >= 32 && lane < 32 + cneg;
+      if (mv_pos || mv_neg) {
+        const int from = mv_pos ? mp + lane : FAR_CAP - 1 - (mq + lane - 32), to = mv_pos ? lane : FAR_CAP - 1 - (lane - 32);
+        R b[4];
+        Rec4<R>::get(farB + from * NW, b);
+        const typename CP::Extra e = CP::load_extra(farX, from);
+        Rec4<R>::put(farB + to * NW, b[0], b[1], b[2], b[3]);
+        CP::store_extra(farX, to, e);
+      }
+    }
+    __syncthreads();
+    // The last leftovers (< UNR of either sign) one at a time, with a wave-uniform trip count: no folded record contributes exactly 0 (k = 0 makes
+    // rsq(0) P = inf 0 = NaN), so they are not padded
+    if (cpos + cneg > 0) {
+      R tacc[T][NF];
+#pragma unroll
+      for (int j = 0; j < T; j++) tacc[j][0] = 0;
+      for (int i = 0; i < cpos; i++) far_folded(tacc, i, std::integral_constant<bool, false>());
+      for (int i = 0; i < cneg; i++) far_folded(tacc, i, std::integral_constant<bool, true>());
+#pragma unroll
+      for (int j = 0; j < T; j++) acc[j][0] += tacc[j][0];
+    }
+  } else if constexpr (sizeof(R) == 8) {
     int carry = 0;   // far records left over from the previous tiles (wave-uniform, < UNR)
     for (int it = 0; it < ntile; it++) {
       const int n = carry + stage_tile(it, carry), m = n & ~(UNR - 1);
