@@ -281,6 +281,27 @@ int sctl_amd_op_set_near(sctl_amd_op* op, int src_dim, int trg_dim, int64_t Nele
 int sctl_amd_op_eval_potential(sctl_amd_op* op, const void* v_src_far, const void* f_near, void* v_trg, int accumulate, int digits, const void* ctx,
                                int ctx_bytes);
 
+/* ---- several densities through the near field and ComputePotential ------------------------------------------------------------- */
+/* nd densities against one near-field operator: U_ = F_ . K_near_ with nd rows in F_ (the reference writes the step as
+ * Matrix::GEMM(U_, F_, K_near_), boundary_integral.txx:1092-1102), every operator entry read from HBM ONCE per pass instead of once
+ * per density, then the scatter and the per-target accumulation (:1129-1140) with a target's indices read once for all rows.
+ * Density-major: F[nd][density_len], U[nd][Ntrg*trg_dim]; row m is what sctl_amd_near_apply_* takes and returns, and every row of U
+ * is ACCUMULATED into.  nd == 1 IS the single-density entry (bit-identical), nd == 0 does nothing, nd < 0 is
+ * SCTL_AMD_ERR_BAD_ARGUMENT; argument errors come back before any device work.  Any nd is legal: a call runs passes of 8 densities
+ * (fp64 and fp32 alike) and a last pass of the narrowest form (2, 4 or 8) that takes what is left, one density left over going through
+ * the single-density kernels.  Within a several-densities pass a row's terms are summed in another order than the single-density
+ * kernel's (fewer partial sums per density), so row m agrees with a single application to rounding, not bit for bit; results are
+ * bit-identical from run to run.  The workspace of a pass belongs to the handle and is allocated on the first several-densities call. */
+int sctl_amd_near_apply_densities_host(sctl_amd_near* op, int nd, const void* F, void* U);                   /* HOST arrays            */
+int sctl_amd_near_apply_densities_device(sctl_amd_near* op, int nd, const void* F, void* U, void* stream);   /* DEVICE arrays, enqueue */
+/* sctl_amd_op_eval_potential (ComputePotential, boundary_integral.txx:608-614) for nd densities, HOST arrays v_src_far[nd][Ns*SrcDim],
+ * f_near[nd][sum(elem_nds_cnt)*SrcDim], v_trg[nd][Nt*trg_dim]: on every device of the handle all densities go down once, the far field
+ * runs as sctl_amd_op_eval_densities does (weights and target normals applied to every row; its pass widths per kernel and precision),
+ * the near field of all rows (passes of up to 8) is accumulated into the far-field result where it lies, and the potential comes up
+ * once.  Errors as sctl_amd_op_eval_potential; nd == 1 is that entry, nd == 0 does nothing after the argument checks. */
+int sctl_amd_op_eval_potential_densities(sctl_amd_op* op, int nd, const void* v_src_far, const void* f_near, void* v_trg, int accumulate,
+                                         int digits, const void* ctx, int ctx_bytes);
+
 int sctl_amd_near_info(const sctl_amd_near* op, int64_t* density_len, int64_t* potential_len, int64_t* near_entries,
                        int64_t* operator_bytes, int64_t* workgroups);
 void sctl_amd_near_destroy(sctl_amd_near* op);

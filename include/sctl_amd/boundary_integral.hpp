@@ -229,7 +229,93 @@ template <class Real, class Kernel> class BoundaryIntegralOp {
     AddMatrixFreeNearField(U, F);
   }
 
+  // ---- several densities (block Krylov solves, several incident fields): F is nd x Dim(0), U nd x Dim(1), row m what the single entry
+  // takes and returns.  The densities go to the devices once and every operator entry of the near field is read once for all rows
+  // (sctl_amd_op_eval_densities, sctl_amd_near_apply_densities_host, sctl_amd_op_eval_potential_densities); GatherFarFieldDensity and
+  // AddMatrixFreeNearField are host work and run per row.  nd = 1 gives what the single entries give, bit for bit. ----
+  void ComputeFarFieldDensities(Matrix<Real>& U, const Matrix<Real>& F) const {
+    SetupBasic();
+    SetupFar();
+    const Long nd = F.Dim(0), Nsrc = X_far.Dim() / COORD_DIM, Ntrg = Xtrg.Dim() / COORD_DIM;
+    SCTL_AMD_ASSERT(nd == 0 || F.Dim(1) == Dim(0));
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    if (U.Dim(0) != nd || U.Dim(1) != Ntrg * KDIM1_) U.ReInit(nd, Ntrg * KDIM1_);
+    U.SetZero();
+    if (!nd || !Ntrg || !Nsrc) return;
+    Matrix<Real> F_far_all;
+    GatherFarFieldDensities(F_far_all, F);
+    CheckStatus(sctl_amd_op_eval_densities(far_op, (int)nd, F_far_all.begin(), U.begin(), /*accumulate*/ 0, fmm_digits(), ker_.GetCtxPtr(), (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_densities");
+  }
+
+  // every row of U is ACCUMULATED into when U has the right shape
+  void ComputeNearInteracDensities(Matrix<Real>& U, const Matrix<Real>& F) const {
+    Setup();
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long nd = F.Dim(0), Ntrg = Xtrg.Dim() / COORD_DIM, Nelem = near_elem_cnt.Dim();
+    SCTL_AMD_ASSERT(nd == 0 || F.Dim(1) == Dim(0));
+    if (U.Dim(0) != nd || U.Dim(1) != Ntrg * KDIM1_) {
+      U.ReInit(nd, Ntrg * KDIM1_);
+      U.SetZero();
+    }
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near || !nd) return;
+    if (!near_op) {
+      const int rc = sctl_amd_near_create(RealTag<Real>::value, DeviceSet::Get()[0], Nelem, (int)KDIM0, (int)KDIM1_, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt),
+                                          PtrOf(K_near_cnt), K_near.Dim() ? (const void*)K_near.begin() : nullptr, Ntrg, PtrOf(near_scatter_index),
+                                          PtrOf(near_trg_cnt), PtrOf(near_trg_dsp), &near_op);
+      CheckStatus(rc, "sctl_amd_near_create");
+    }
+    CheckStatus(sctl_amd_near_apply_densities_host(near_op, (int)nd, F.begin(), U.begin()), "sctl_amd_near_apply_densities_host");
+    AddMatrixFreeNearFieldRows(U, F);
+  }
+
+  void ComputePotentialDensities(Matrix<Real>& U, const Matrix<Real>& F) const {
+    Setup();
+    const Long nd = F.Dim(0), Nelem = near_elem_cnt.Dim();
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near || !far_op || !nd) {   // as ComputePotential: the two legs as they are
+      ComputeFarFieldDensities(U, F);
+      ComputeNearInteracDensities(U, F);
+      return;
+    }
+    SCTL_AMD_ASSERT(F.Dim(1) == Dim(0));
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long Ntrg = Xtrg.Dim() / COORD_DIM;
+    Matrix<Real> F_far_all;
+    GatherFarFieldDensities(F_far_all, F);
+    if (U.Dim(0) != nd || U.Dim(1) != Ntrg * KDIM1_) U.ReInit(nd, Ntrg * KDIM1_);
+    if (!near_attached) {
+      CheckStatus(sctl_amd_op_set_near(far_op, (int)KDIM0, (int)KDIM1_, Nelem, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt), PtrOf(K_near_cnt),
+                                       K_near.Dim() ? (const void*)K_near.begin() : nullptr, PtrOf(near_scatter_index), PtrOf(near_trg_cnt), PtrOf(near_trg_dsp)),
+                  "sctl_amd_op_set_near");
+      near_attached = true;
+    }
+    CheckStatus(sctl_amd_op_eval_potential_densities(far_op, (int)nd, F_far_all.begin(), F.begin(), U.begin(), /*accumulate*/ 0, fmm_digits(), ker_.GetCtxPtr(),
+                                                     (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_potential_densities");
+    AddMatrixFreeNearFieldRows(U, F);
+  }
+
  private:
+  // GatherFarFieldDensity, one row at a time, into F_far_all (nd x far-field density length)
+  void GatherFarFieldDensities(Matrix<Real>& F_far_all, const Matrix<Real>& F) const {
+    const Long nd = F.Dim(0), n_far = (X_far.Dim() / COORD_DIM) * KDIM0;
+    F_far_all.ReInit(nd, n_far);
+    for (Long m = 0; m < nd; m++) {
+      const Vector<Real> f(F.Dim(1), (Iterator<Real>)F[m], false);
+      GatherFarFieldDensity(f);
+      std::copy(F_far.begin(), F_far.begin() + n_far, F_far_all[m]);
+    }
+  }
+  void AddMatrixFreeNearFieldRows(Matrix<Real>& U, const Matrix<Real>& F) const {
+    for (Long m = 0; m < F.Dim(0); m++) {
+      const Vector<Real> f(F.Dim(1), (Iterator<Real>)F[m], false);
+      Vector<Real> u(U.Dim(1), U[m], false);
+      AddMatrixFreeNearField(u, f);
+    }
+  }
+
   // Density at the far-field quadrature nodes, one element list at a time (each list owns a contiguous run of surface nodes and
   // of far-field nodes); the quadrature weights are NOT applied here: they live on the device (boundary_integral.txx:1040-1052).
   void GatherFarFieldDensity(const Vector<Real>& F) const {

@@ -29,7 +29,7 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_set_debug", "sctl_amd_comm_create", "sctl_amd_comm_info", "sctl_amd_comm_allgatherv_host", "sctl_amd_comm_barrier", "sctl_amd_comm_selftest", "sctl_amd_comm_destroy",
            "sctl_amd_op_set_sources_dist", "sctl_amd_op_eval_dist", "sctl_amd_op_set_near", "sctl_amd_op_eval_potential", "sctl_amd_lists_create", "sctl_amd_lists_eval_device", "sctl_amd_lists_eval_host", "sctl_amd_lists_info", "sctl_amd_lists_destroy",
            "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host", "sctl_amd_eval_densities_device", "sctl_amd_eval_densities_host", "sctl_amd_op_eval_densities",
-           "sctl_amd_eval_densities_plan"]
+           "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities"]
 
 
 class SctlAmdError(RuntimeError):
@@ -121,6 +121,9 @@ def lib():
     L.sctl_amd_eval_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_op_eval_densities.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sctl_amd_near_apply_densities_host.argtypes = [vp, ci, vp, vp]
+    L.sctl_amd_near_apply_densities_device.argtypes = [vp, ci, vp, vp, vp]
+    L.sctl_amd_op_eval_potential_densities.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, ci]
     L.sctl_amd_eval_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(i64)] * 2
     _LIB = L
     return L
@@ -523,6 +526,24 @@ class DirectOp:
                                                 1 if accumulate else 0, digits, cp, cb), "op_eval_potential")
         return v_trg
 
+    def eval_potential_densities(self, V_src_far, F_near, V_trg=None, accumulate=False, digits=-1):
+        """eval_potential() for nd densities in one pass over the devices (sctl_amd_op_eval_potential_densities): V_src_far of shape
+        (nd, Ns*SrcDim), F_near of shape (nd, near density length), returns (nd, Nt*trg_dim)."""
+        k1 = self._near_k1
+        if V_src_far.ndim != 2 or V_src_far.shape[1] != self.Ns * self.info["k0"]:
+            raise SctlAmdError("V_src_far must have shape (nd, %d)" % (self.Ns * self.info["k0"]))
+        nd = V_src_far.shape[0]
+        if F_near.shape != (nd, self._near_len):
+            raise SctlAmdError("F_near must have shape (%d, %d)" % (nd, self._near_len))
+        if V_trg is None or V_trg.shape != (nd, self.Nt * k1):
+            V_trg = np.zeros((nd, self.Nt * k1), dtype=self.dtype)
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_potential_densities(self._h, nd, _np_ptr(V_src_far, self.dtype, nd * self.Ns * self.info["k0"], "V_src_far"),
+                                                          _np_ptr(F_near, self.dtype, nd * self._near_len, "F_near"),
+                                                          _np_ptr(V_trg, self.dtype, nd * self.Nt * k1, "V_trg"), 1 if accumulate else 0, digits, cp, cb),
+               "op_eval_potential_densities")
+        return V_trg
+
     def close(self):
         if self._h:
             lib().sctl_amd_op_destroy(self._h)
@@ -576,6 +597,35 @@ class NearOp:
             st = stream if stream is not None else torch.cuda.current_stream()
             _check(lib().sctl_amd_near_apply_device(self._h, _t_ptr(F, tdt, self.density_len, "F"), _t_ptr(U, tdt, self.potential_len, "U"),
                                                     C.c_void_p(st.cuda_stream)), "near_apply_device")
+        return U
+
+    def apply_densities(self, F, U=None):
+        """apply() for nd densities with the operator read once per pass (sctl_amd_near_apply_densities_host): F of shape
+        (nd, density_len); every row of U (nd, potential_len) is accumulated into, U=None starts from zero."""
+        F = np.ascontiguousarray(F, dtype=self.dtype)
+        if F.ndim != 2 or F.shape[1] != self.density_len:
+            raise SctlAmdError("densities must have shape (nd, %d)" % self.density_len)
+        nd = F.shape[0]
+        if U is None:
+            U = np.zeros((nd, self.potential_len), dtype=self.dtype)
+        if U.shape != (nd, self.potential_len) or U.dtype != self.dtype or not U.flags.c_contiguous:
+            raise SctlAmdError("potentials must be a contiguous %s array of shape (%d, %d)" % (self.dtype, nd, self.potential_len))
+        p = lambda a: None if a.size == 0 else a.ctypes.data_as(C.c_void_p)
+        _check(lib().sctl_amd_near_apply_densities_host(self._h, nd, p(F), p(U)), "near_apply_densities_host")
+        return U
+
+    def apply_densities_device(self, F, U, stream=None):
+        """The same on torch CUDA tensors of shapes (nd, density_len) and (nd, potential_len), enqueued on `stream` (default: torch's
+        current stream); every row of U is accumulated into."""
+        import torch
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if F.dim() != 2 or U.dim() != 2 or U.shape[0] != F.shape[0]:
+            raise SctlAmdError("densities and potentials must have shapes (nd, %d) and (nd, %d)" % (self.density_len, self.potential_len))
+        nd = F.shape[0]
+        with torch.cuda.device(F.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_near_apply_densities_device(self._h, nd, _t_ptr(F, tdt, nd * self.density_len, "F"), _t_ptr(U, tdt, nd * self.potential_len, "U"),
+                                                              C.c_void_p(st.cuda_stream)), "near_apply_densities_device")
         return U
 
     def close(self):

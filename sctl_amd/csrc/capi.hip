@@ -606,6 +606,7 @@ struct sctl_amd_op {
   // (near targets) of every element block that fall into that device's target slab, so far + near are added ON the device
   std::vector<sctl_amd_near*> near;
   std::vector<void*> near_f;      // device copy of the near density (element nodes x SrcDim), one per device
+  std::vector<size_t> near_f_cap; // its bytes: one density after set_near, nd of them after a several-densities evaluation
   int64_t near_f_len = 0;
   int near_trg_dim = 0;
 };
@@ -1282,6 +1283,7 @@ static void op_release_near(sctl_amd_op* op) {
   }
   op->near.clear();
   op->near_f.clear();
+  op->near_f_cap.clear();
   op->near_f_len = 0;
   op->near_trg_dim = 0;
 }
@@ -1328,6 +1330,7 @@ int sctl_amd_op_set_near(sctl_amd_op* op, int src_dim, int trg_dim, int64_t Nele
   for (int64_t i = 0; i < Nt; i++) slot[op->perm.empty() ? (size_t)i : (size_t)op->perm[(size_t)i]] = i;
   op->near.assign((size_t)G, nullptr);
   op->near_f.assign((size_t)G, nullptr);
+  op->near_f_cap.assign((size_t)G, 0);
   op->near_f_len = f_len;
   op->near_trg_dim = trg_dim;
   const char* Kh = (const char*)K_near;
@@ -1371,7 +1374,7 @@ int sctl_amd_op_set_near(sctl_amd_op* op, int src_dim, int trg_dim, int64_t Nele
                                   sc_g.empty() ? nullptr : sc_g.data(), tc_g.data(), td_g.data(), &op->near[(size_t)g]);
     if (rc == SCTL_AMD_OK && f_len > 0) {
       DeviceScope scope(d.device);
-      if (scope.err != hipSuccess || hipMalloc(&op->near_f[(size_t)g], (size_t)f_len * rs) != hipSuccess) rc = fail(SCTL_AMD_ERR_HIP, "cannot allocate the near-field density on device " + std::to_string(d.device));
+      if (scope.err != hipSuccess || grow(&op->near_f[(size_t)g], &op->near_f_cap[(size_t)g], (size_t)f_len * rs) != hipSuccess) rc = fail(SCTL_AMD_ERR_HIP, "cannot allocate the near-field density on device " + std::to_string(d.device));
     }
     if (rc != SCTL_AMD_OK) { const std::string msg = g_err; op_release_near(op); g_err = msg; return rc; }
   }
@@ -1450,16 +1453,12 @@ int sctl_amd_eval_densities_host(int kernel, int real, int nd, int64_t Nt, int64
   return SCTL_AMD_OK;
 }
 
-int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void* v_trg, int accumulate, int digits, const void* ctx, int ctx_bytes) {
-  if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
-  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+// far field (+ the attached near field when f_near != nullptr) of nd >= 2 densities, density-major, all rows of the potential back to the host
+// once: the per-device body of sctl_amd_op_eval_densities and sctl_amd_op_eval_potential_densities (arguments checked by the callers).
+static int op_eval_densities_impl(sctl_amd_op* op, int nd, const void* v_src, const void* f_near, void* v_trg, int accumulate, int digits, const void* ctx) {
   const KernelEntry& k = *op->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return fail(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
-  if (nd > 0 && ((op->Ns > 0 && !v_src) || (op->Nt > 0 && !v_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
-  if (nd == 0) return SCTL_AMD_OK;
-  if (nd == 1) return sctl_amd_op_eval(op, v_src, v_trg, accumulate, digits, ctx, ctx_bytes);
   const size_t rs = (op->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t near_bytes = f_near ? (size_t)nd * op->near_f_len * rs : 0;
   const int64_t Ns = op->Ns, Nt = op->Nt;
   const int k1 = op->have_trg_normals ? k.k1 / 3 : k.k1;   // components per target that go back to the host
   return op_for_each_device(op, [&](OpDevice& d) -> int {
@@ -1470,8 +1469,13 @@ int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void*
     const size_t fbytes = (size_t)nd * Ns * k.k0 * rs, vbytes = (size_t)nd * nt * k.k1 * rs, obytes = (size_t)nd * nt * k1 * rs;
     HIP_TRY(grow(&d.f, &d.cap_f, fbytes));
     HIP_TRY(grow(&d.v, &d.cap_v, vbytes));
-    HIP_TRY(d.stage.reserve(pad256(fbytes) + pad256(obytes)));
+    HIP_TRY(d.stage.reserve(pad256(fbytes) + pad256(near_bytes) + pad256(obytes)));
     HIP_TRY(upload(d.f, v_src, fbytes, d.stage, d.st));
+    const size_t g = (size_t)(&d - op->devs.data());
+    if (near_bytes) {
+      HIP_TRY(grow(&op->near_f[g], &op->near_f_cap[g], near_bytes));
+      HIP_TRY(upload(op->near_f[g], f_near, near_bytes, d.stage, d.st));
+    }
     const unsigned nbf = (unsigned)((Ns * k.k0 + kBlock - 1) / kBlock), nbo = (unsigned)((nt * k1 + kBlock - 1) / kBlock);
     if (op->have_weights && Ns > 0) {   // every density x the quadrature weights
       for (int m = 0; m < nd; m++) {
@@ -1505,6 +1509,10 @@ int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void*
       HIP_TRY(hipGetLastError());
       result = d.u;
     }
+    if (f_near && op->near[g]) {   // the near-zone correction of this slab's targets, every row added where its far field lies (rows nt * k1 apart)
+      rc = sctl_amd_near_apply_densities_device(op->near[g], nd, op->near_f[g], result, d.st);
+      if (rc) return rc;
+    }
     const char* out = d.stage.take(obytes);
     HIP_TRY(hipMemcpyAsync((void*)out, result, obytes, hipMemcpyDeviceToHost, d.st));
     HIP_TRY(hipStreamSynchronize(d.st));
@@ -1527,6 +1535,36 @@ int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void*
     else scatter((float*)v_trg, (const float*)out);
     return SCTL_AMD_OK;
   });
+}
+
+int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void* v_trg, int accumulate, int digits, const void* ctx, int ctx_bytes) {
+  if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  const KernelEntry& k = *op->k;
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return fail(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (nd > 0 && ((op->Ns > 0 && !v_src) || (op->Nt > 0 && !v_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
+  if (nd == 0) return SCTL_AMD_OK;
+  if (nd == 1) return sctl_amd_op_eval(op, v_src, v_trg, accumulate, digits, ctx, ctx_bytes);
+  return op_eval_densities_impl(op, nd, v_src, nullptr, v_trg, accumulate, digits, ctx);
+}
+
+int sctl_amd_op_eval_potential_densities(sctl_amd_op* op, int nd, const void* v_src_far, const void* f_near, void* v_trg, int accumulate, int digits,
+                                         const void* ctx, int ctx_bytes) {
+  if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  const KernelEntry& k = *op->k;
+  if (op->near.empty()) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "no near-field operator attached: call sctl_amd_op_set_near first");
+  if (op->near_trg_dim != (op->have_trg_normals ? k.k1 / 3 : k.k1))
+    return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "the attached near-field operator has another potential dimension than the far field delivers");
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return fail(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (nd > 0 && ((op->Ns > 0 && !v_src_far) || (op->Nt > 0 && !v_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
+  if (nd > 0 && op->near_f_len > 0 && !f_near) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field density");
+  if (nd == 0) return SCTL_AMD_OK;
+  if (nd == 1) return sctl_amd_op_eval_potential(op, v_src_far, f_near, v_trg, accumulate, digits, ctx, ctx_bytes);
+  static const char nothing = 0;   // an operator without element nodes still takes the near path (which then adds nothing)
+  return op_eval_densities_impl(op, nd, v_src_far, op->near_f_len == 0 ? (const void*)&nothing : f_near, v_trg, accumulate, digits, ctx);
 }
 
 int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* densities_per_pass, int* passes, int* trg_per_lane,

@@ -100,15 +100,137 @@ __global__ void __launch_bounds__(256) near_accumulate_kernel(int64_t ntrg, int 
   U[idx] = acc;
 }
 
+// ---- several densities against one operator (sctl_amd_near_apply_densities_*): U_[m] = F_[m] . K_near_, Matrix::GEMM(U_, F_, K_near_) with
+// M rows in F_ (boundary_integral.txx:1092-1102), every operator entry read ONCE for the M densities ------------------------------------------
+// Rows 0, 1, ... of one column for M densities: 8 row loads in flight per lane as in near_column_sum, each entry multiplied into M
+// accumulators.  The densities of a row are wave-uniform (Fe and f_stride are: scalar loads, 8 consecutive rows of a density at a time);
+// NP partial sums per density keep M * NP accumulators in registers (fp64, M = 8, NP = 2: 32 VGPRs), so the order in which a row's terms
+// are added differs from the single-density kernel's.  Densities nact .. M-1 of a last, partly filled pass repeat density nact-1 and
+// are not stored.
+template <class R, int M, int NP>
+__device__ __forceinline__ void near_column_sums(const R* __restrict__ Kc, const R* __restrict__ Fe, int64_t f_stride, int nact, int64_t ld, int src_dof,
+                                                 R (&out)[M]) {
+  static_assert(NP == 2 || NP == 4, "the reductions below are written for 2 or 4 partial sums");
+  constexpr int UNR = 8;
+  R acc[M][NP];
+  const R* Fm[M];
+#pragma unroll
+  for (int m = 0; m < M; m++) {
+    Fm[m] = Fe + (int64_t)(m < nact ? m : nact - 1) * f_stride;
+#pragma unroll
+    for (int p = 0; p < NP; p++) acc[m][p] = 0;
+  }
+  int s = 0;
+  for (; s + UNR <= src_dof; s += UNR) {     // whole groups of 8 rows: no predicates
+    R kv[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; u++) kv[u] = __builtin_nontemporal_load(Kc + (int64_t)(s + u) * ld);
+#pragma unroll
+    for (int u = 0; u < UNR; u++)
+#pragma unroll
+      for (int m = 0; m < M; m++) acc[m][u % NP] += Fm[m][s + u] * kv[u];
+  }
+  if (s < src_dof) {                         // the last 1 .. 7 rows
+    R kv[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; u++) kv[u] = (s + u < src_dof) ? __builtin_nontemporal_load(Kc + (int64_t)(s + u) * ld) : R(0);
+#pragma unroll
+    for (int u = 0; u < UNR; u++)
+#pragma unroll
+      for (int m = 0; m < M; m++) acc[m][u % NP] += ((s + u < src_dof) ? Fm[m][s + u] : R(0)) * kv[u];
+  }
+#pragma unroll
+  for (int m = 0; m < M; m++) out[m] = (NP == 2) ? acc[m][0] + acc[m][NP - 1] : (acc[m][0] + acc[m][1]) + (acc[m][NP - 2] + acc[m][NP - 1]);
+}
+
+// near_gemv_kernel's work list and lane mapping, M densities per pass: U_near[m * un_stride + u_off + t] = sum_s F[m * f_stride + f_off + s] *
+// K[k_off + s * trg_dof + t].  The wave index of a narrow item goes through readfirstlane, so that the item and with it the density
+// addresses are known to be wave-uniform.
+template <class R, int M>
+__global__ void __launch_bounds__(kNearBlock) near_gemm_kernel(const NearWork* __restrict__ wide_work, int64_t n_wide, const NearWork* __restrict__ narrow_work,
+                                                               int64_t n_narrow, const R* __restrict__ K, const R* __restrict__ F, int64_t f_stride, int nact,
+                                                               R* __restrict__ U_near, int64_t un_stride) {
+  constexpr int NP = (M >= 8) ? 2 : 4;
+  for (int64_t wi = blockIdx.x; wi < n_wide; wi += gridDim.x) {
+    const NearWork w = wide_work[wi];
+    const int t = w.t0 + (int)threadIdx.x;
+    if (t < w.trg_dof) {
+      R u[M];
+      near_column_sums<R, M, NP>(K + w.k_off + t, F + w.f_off, f_stride, nact, w.trg_dof, w.src_dof, u);
+#pragma unroll
+      for (int m = 0; m < M; m++)
+        if (m < nact) U_near[(int64_t)m * un_stride + w.u_off + t] = u[m];
+    }
+  }
+  const int lane = threadIdx.x & (kCols - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kCols));
+  for (int64_t wi = (int64_t)blockIdx.x * kRowGroups + wave; wi < n_narrow; wi += (int64_t)gridDim.x * kRowGroups) {
+    const NearWork w = narrow_work[wi];
+    const int t = w.t0 + lane;
+    if (t < w.trg_dof) {
+      R u[M];
+      near_column_sums<R, M, NP>(K + w.k_off + t, F + w.f_off, f_stride, nact, w.trg_dof, w.src_dof, u);
+#pragma unroll
+      for (int m = 0; m < M; m++)
+        if (m < nact) U_near[(int64_t)m * un_stride + w.u_off + t] = u[m];
+    }
+  }
+}
+
+// near_accumulate_kernel for M densities: a target's displacement, count and scatter indices are read once and used for every row;
+// each row adds its entries in the order of the scattered array, as the single-density kernel does.
+template <class R, int M>
+__global__ void __launch_bounds__(256) near_accumulate_multi_kernel(int64_t ntrg, int k1, int nact, const int64_t* __restrict__ scatter,
+                                                                    const int64_t* __restrict__ trg_cnt, const int64_t* __restrict__ trg_dsp,
+                                                                    const R* __restrict__ U_near, int64_t un_stride, R* __restrict__ U, int64_t u_stride) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ntrg * k1) return;
+  const int64_t i = idx / k1;
+  const int k = (int)(idx - i * k1);
+  const int64_t p0 = trg_dsp[i], p1 = p0 + trg_cnt[i];
+  if (p1 == p0) return;
+  R acc[M];
+#pragma unroll
+  for (int m = 0; m < M; m++) acc[m] = (m < nact) ? U[(int64_t)m * u_stride + idx] : R(0);
+  int64_t p = p0;
+  for (; p + 2 <= p1; p += 2) {      // two index loads, then 2 M independent gathers
+    const int64_t j0 = scatter[p] * k1 + k, j1 = scatter[p + 1] * k1 + k;
+    R v0[M], v1[M];
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const int64_t row = (int64_t)(m < nact ? m : nact - 1) * un_stride;
+      v0[m] = U_near[row + j0];
+      v1[m] = U_near[row + j1];
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m] = (acc[m] + v0[m]) + v1[m];
+  }
+  if (p < p1) {
+    const int64_t j0 = scatter[p] * k1 + k;
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m] += U_near[(int64_t)(m < nact ? m : nact - 1) * un_stride + j0];
+  }
+#pragma unroll
+  for (int m = 0; m < M; m++)
+    if (m < nact) U[(int64_t)m * u_stride + idx] = acc[m];
+}
+
 struct DevMem {
   void* p = nullptr;
   ~DevMem() { if (p) (void)hipFree(p); }
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
+  hipError_t realloc(size_t bytes) {   // (hipFree waits for the work that still uses the old block)
+    if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
+    return alloc(bytes);
+  }
 };
 struct PinMem {
   void* p = nullptr;
   ~PinMem() { if (p) (void)hipHostFree(p); }
   hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocPortable); }
+  hipError_t realloc(size_t bytes) {
+    if (p) { hipError_t e = hipHostFree(p); p = nullptr; if (e != hipSuccess) return e; }
+    return alloc(bytes);
+  }
 };
 
 }  // namespace
@@ -122,6 +244,12 @@ struct sctl_amd_near {
   DevMem K, work, scatter, trg_cnt, trg_dsp, F, U_near, U;   // work: the wide items, then the narrow ones
   int64_t n_wide = 0, n_narrow = 0;
   PinMem stage;                 // F down, U up (host entry)
+  // several densities: allocated on first use, never by sctl_amd_near_create
+  DevMem U_near_m;              // [m_cap][n_near * k1], m_cap = the widest pass used so far; zero-filled when grown
+  int m_cap = 0;
+  DevMem F_m, U_m;              // [nd_cap] densities and potentials of the host entry
+  PinMem stage_m;
+  int nd_cap = 0;
   hipStream_t st = nullptr;
   ~sctl_amd_near() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -146,6 +274,64 @@ int apply_on_stream(sctl_amd_near* h, const R* F, R* U, hipStream_t st) {
                        (const int64_t*)h->trg_cnt.p, (const int64_t*)h->trg_dsp.p, (const R*)h->U_near.p, U);
     NEAR_TRY(hipGetLastError());
   }
+  return SCTL_AMD_OK;
+}
+
+
+// the pass for `left` densities still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
+inline int near_pass_width(int left) { return left <= 2 ? 2 : left <= 4 ? 4 : 8; }
+
+template <class R, int M>
+int near_pass(sctl_amd_near* h, int nact, const R* F, R* U, hipStream_t st) {
+  const int64_t un_stride = h->n_near * h->k1;
+  if (h->nwork > 0) {
+    const int64_t resident = (int64_t)h->cus * 8;
+    const int64_t groups = h->n_wide + (h->n_narrow + kRowGroups - 1) / kRowGroups;
+    const unsigned grid = (unsigned)(groups < resident * 4 ? groups : resident * 4);
+    const NearWork* wl = (const NearWork*)h->work.p;
+    hipLaunchKernelGGL((near_gemm_kernel<R, M>), dim3(grid), dim3(kNearBlock), 0, st, wl, h->n_wide, wl + h->n_wide, h->n_narrow, (const R*)h->K.p, F, h->f_len, nact,
+                       (R*)h->U_near_m.p, un_stride);
+    NEAR_TRY(hipGetLastError());
+  }
+  const int64_t n = h->ntrg * h->k1;
+  hipLaunchKernelGGL((near_accumulate_multi_kernel<R, M>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->ntrg, h->k1, nact, (const int64_t*)h->scatter.p,
+                     (const int64_t*)h->trg_cnt.p, (const int64_t*)h->trg_dsp.p, (const R*)h->U_near_m.p, un_stride, U, n);
+  NEAR_TRY(hipGetLastError());
+  return SCTL_AMD_OK;
+}
+
+// nd >= 2 densities, density-major: passes of 8, the last pass on the narrowest form that takes what is left; a single density left over
+// goes through the single-density kernels.
+template <class R>
+int apply_densities_on_stream(sctl_amd_near* h, int nd, const R* F, R* U, hipStream_t st) {
+  (void)hipGetLastError();
+  if (h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  const int widest = near_pass_width(nd);
+  if (widest > h->m_cap) {   // U_near for the widest pass of this call; the runs of matrix-free elements are never written and stay zero
+    const size_t bytes = (size_t)widest * h->n_near * h->k1 * sizeof(R);
+    h->m_cap = 0;
+    NEAR_TRY(h->U_near_m.realloc(bytes));
+    NEAR_TRY(hipMemsetAsync(h->U_near_m.p, 0, bytes, st));
+    h->m_cap = widest;
+  }
+  const int64_t u_len = h->ntrg * h->k1;
+  for (int m0 = 0; m0 < nd;) {
+    const int left = nd - m0;
+    const R* Fp = F + (int64_t)m0 * h->f_len;
+    R* Up = U + (int64_t)m0 * u_len;
+    if (left == 1) return apply_on_stream<R>(h, Fp, Up, st);
+    const int M = near_pass_width(left), nact = left < M ? left : M;
+    const int rc = (M == 2) ? near_pass<R, 2>(h, nact, Fp, Up, st) : (M == 4) ? near_pass<R, 4>(h, nact, Fp, Up, st) : near_pass<R, 8>(h, nact, Fp, Up, st);
+    if (rc) return rc;
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+
+int check_apply_densities(const sctl_amd_near* h, int nd, const void* F, const void* U) {
+  if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  if (nd > 0 && ((h->f_len > 0 && !F) || (h->ntrg > 0 && !U))) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
   return SCTL_AMD_OK;
 }
 
@@ -257,6 +443,47 @@ int sctl_amd_near_apply_host(sctl_amd_near* h, const void* F, void* U) {
   NEAR_TRY(hipMemcpyAsync(su, h->U.p, bu, hipMemcpyDeviceToHost, h->st));
   NEAR_TRY(hipStreamSynchronize(h->st));
   const int64_t n = h->ntrg * h->k1;                       // U += near field (boundary_integral.txx:1131-1140)
+  if (h->real == SCTL_AMD_F64) { double* d = (double*)U; const double* s = (const double*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
+  else { float* d = (float*)U; const float* s = (const float*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_near_apply_densities_device(sctl_amd_near* h, int nd, const void* F, void* U, void* stream) {
+  const int rc = check_apply_densities(h, nd, F, U);
+  if (rc || nd == 0) return rc;
+  if (nd == 1) return sctl_amd_near_apply_device(h, F, U, stream);
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  if (h->real == SCTL_AMD_F64) return apply_densities_on_stream<double>(h, nd, (const double*)F, (double*)U, (hipStream_t)stream);
+  return apply_densities_on_stream<float>(h, nd, (const float*)F, (float*)U, (hipStream_t)stream);
+}
+
+int sctl_amd_near_apply_densities_host(sctl_amd_near* h, int nd, const void* F, void* U) {
+  const int rc0 = check_apply_densities(h, nd, F, U);
+  if (rc0 || nd == 0) return rc0;
+  if (nd == 1) return sctl_amd_near_apply_host(h, F, U);
+  if (h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t bf = (size_t)nd * h->f_len * rs, bu = (size_t)nd * h->ntrg * h->k1 * rs;
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  if (nd > h->nd_cap) {
+    h->nd_cap = 0;
+    NEAR_TRY(h->F_m.realloc(bf));
+    NEAR_TRY(h->U_m.realloc(bu));
+    NEAR_TRY(h->stage_m.realloc(bf + bu + 512));
+    h->nd_cap = nd;
+  }
+  char* sf = (char*)h->stage_m.p;
+  char* su = sf + ((bf + 255) & ~(size_t)255);
+  std::memcpy(sf, F, bf);
+  NEAR_TRY(hipMemcpyAsync(h->F_m.p, sf, bf, hipMemcpyHostToDevice, h->st));
+  NEAR_TRY(hipMemsetAsync(h->U_m.p, 0, bu, h->st));
+  const int rc = sctl_amd_near_apply_densities_device(h, nd, h->F_m.p, h->U_m.p, h->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  NEAR_TRY(hipMemcpyAsync(su, h->U_m.p, bu, hipMemcpyDeviceToHost, h->st));
+  NEAR_TRY(hipStreamSynchronize(h->st));
+  const int64_t n = (int64_t)nd * h->ntrg * h->k1;         // every row: U += near field
   if (h->real == SCTL_AMD_F64) { double* d = (double*)U; const double* s = (const double*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
   else { float* d = (float*)U; const float* s = (const float*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
   return SCTL_AMD_OK;
