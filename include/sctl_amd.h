@@ -337,6 +337,25 @@ int sctl_amd_eval_lists_host(int kernel, int real, int64_t nlists, const int64_t
                              const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                              const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device);
 
+/* Several densities over the lists of one plan (the several-densities text above applies): density-major v_src[nd][Ns*SrcDim] and
+ * v_trg[nd][Nt*TrgDim], every row ACCUMULATED into.  The plan does not depend on nd: one handle serves the single-density entries and any
+ * nd.  nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, nd == 1 IS sctl_amd_lists_eval_* (bit-identical results); argument and
+ * context errors come back before any device work, with the codes of sctl_amd_lists_eval_*; a plan without work items returns OK without a
+ * device.  A call is ONE launch per pass: passes of the kernel's widest form (8, 4 or 2 densities, per kernel and precision: DESIGN.md
+ * §4.6), then the narrowest form that holds the rest; a single density left over takes the single-density list kernel, and a plugin
+ * kernel (no several-densities form) is evaluated one density at a time on the same stream.  Within a several-densities pass a row's
+ * terms may be summed in another grouping than the single-density kernel's (rel-L2 ~1e-16 in fp64); results are bit-identical from run to
+ * run.  fp32 runs the exact vector-pipe pair.  The counters grow by nd x pairs.  _host: coordinates and normals are staged once, the nd
+ * density rows in one transfer; sources that ARE the targets (one array) keep one device copy. */
+int sctl_amd_lists_eval_densities_device(sctl_amd_lists* plan, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                                         void* v_trg, int digits, const void* ctx, int ctx_bytes, void* stream);
+int sctl_amd_lists_eval_densities_host(sctl_amd_lists* plan, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                                       void* v_trg, int digits, const void* ctx, int ctx_bytes);
+/* One-shot form (plan, evaluate, release), HOST arrays. */
+int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
+                                       const int64_t* src_off, const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src,
+                                       const void* n_src, const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device);
+
 /* ---- accounting (the reference's Profile::IncrementCounter(FLOP, Ns*Nt*FLOPS()), generic-kernel.txx:188) ---- */
 /* Process-wide counters, updated atomically by every eval / kernel_matrix call. */
 void sctl_amd_counters(int64_t* pair_interactions, int64_t* sctl_flops);

@@ -137,6 +137,33 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_lists_host");
   }
 
+  // EvalLists for several densities in one launch per pass (sctl_amd_eval_lists_densities_host): row m of F (nd x Ns*SrcDim) is a density,
+  // row m of U (nd x Nt*TrgDim) what EvalLists gives for it.  U follows EvalDensities' rule: the right size is accumulated into, any other
+  // is resized and zeroed.  nd == 1 is EvalLists' own path.
+  template <class Real, Integer digits = -1>
+  void EvalListsDensities(Matrix<Real>& U, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Matrix<Real>& F,
+                          const Vector<Long>& trg_off, const Vector<Long>& trg_cnt, const Vector<Long>& src_off, const Vector<Long>& src_cnt) const {
+    static_assert(sizeof(Long) == sizeof(int64_t), "Long must be 64 bits wide");
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nl = trg_off.Dim(), nd = F.Dim(0);
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(F.Dim(1) == Ns * KDIM0);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(trg_cnt.Dim() == nl && src_off.Dim() == nl && src_cnt.Dim() == nl);
+    SCTL_AMD_ASSERT(nd <= 0x7fffffff);
+    if (U.Dim(0) != nd || U.Dim(1) != Nt * KDIM1) {
+      U.ReInit(nd, Nt * KDIM1);
+      U.SetZero();
+    }
+    if (!nl || !nd) return;
+    RequireSupported();
+    auto i64 = [](const Vector<Long>& v) { return reinterpret_cast<const int64_t*>(&v[0]); };
+    const int rc = sctl_amd_eval_lists_densities_host(DeviceKernelId(), RealTag<Real>::value, (int)nd, nl, i64(trg_off), i64(trg_cnt), i64(src_off), i64(src_cnt),
+                                                      Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, F.begin(), U.begin(), (int)digits,
+                                                      ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_lists_densities_host");
+  }
+
   // Several densities on the same sources and targets in one evaluation (sctl_amd_eval_densities_host; not in the reference, whose callers
   // call Eval once per density): row m of F (nd x Ns*SrcDim) is a density, row m of U (nd x Nt*TrgDim) its potential — what Eval gives for
   // that row, with the density-independent work of a pair done once for several rows.  U follows Eval's rule: the right size is accumulated

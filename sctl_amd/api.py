@@ -29,7 +29,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_set_debug", "sctl_amd_comm_create", "sctl_amd_comm_info", "sctl_amd_comm_allgatherv_host", "sctl_amd_comm_barrier", "sctl_amd_comm_selftest", "sctl_amd_comm_destroy",
            "sctl_amd_op_set_sources_dist", "sctl_amd_op_eval_dist", "sctl_amd_op_set_near", "sctl_amd_op_eval_potential", "sctl_amd_lists_create", "sctl_amd_lists_eval_device", "sctl_amd_lists_eval_host", "sctl_amd_lists_info", "sctl_amd_lists_destroy",
            "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host", "sctl_amd_eval_densities_device", "sctl_amd_eval_densities_host", "sctl_amd_op_eval_densities",
-           "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities"]
+           "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities",
+           "sctl_amd_lists_eval_densities_device", "sctl_amd_lists_eval_densities_host", "sctl_amd_eval_lists_densities_host"]
 
 
 class SctlAmdError(RuntimeError):
@@ -118,6 +119,9 @@ def lib():
     L.sctl_amd_lists_destroy.restype = None
     L.sctl_amd_eval_lists_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_eval_lists_device.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_lists_eval_densities_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_lists_eval_densities_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, ci]
+    L.sctl_amd_eval_lists_densities_host.argtypes = [ci, ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_eval_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_op_eval_densities.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
@@ -686,6 +690,42 @@ class ListsPlan:
                                                     _t_ptr(v_trg, tdt, self.Nt * i["k1"], "v_trg"), digits, cp, cb, C.c_void_p(st.cuda_stream)), "lists_eval_device")
         return v_trg
 
+    def eval_densities_host(self, r_trg, r_src, n_src, F, V_trg=None, digits=-1):
+        """eval_host() for nd densities in one launch per pass (sctl_amd_lists_eval_densities_host): F of shape (nd, Ns*SrcDim), returns
+        (nd, Nt*k1); a V_trg of that shape is accumulated into, otherwise a fresh zeroed result is returned."""
+        dt, i = self.dtype, self.info
+        F = np.asarray(F)
+        if F.ndim != 2 or F.shape[1] != self.Ns * i["k0"]:
+            raise SctlAmdError("densities must have shape (nd, %d)" % (self.Ns * i["k0"]))
+        nd = F.shape[0]
+        if V_trg is None or V_trg.shape != (nd, self.Nt * i["k1"]):
+            V_trg = np.zeros((nd, self.Nt * i["k1"]), dtype=dt)
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        _check(lib().sctl_amd_lists_eval_densities_host(self._h, nd, _np_ptr(r_trg, dt, self.Nt * 3, "r_trg"), _np_ptr(r_src, dt, self.Ns * 3, "r_src"),
+                                                        _np_ptr(n_src, dt, self.Ns * i["nd"], "n_src"), _np_ptr(F, dt, nd * self.Ns * i["k0"], "F"),
+                                                        _np_ptr(V_trg, dt, nd * self.Nt * i["k1"], "V_trg"), digits, cp, cb), "lists_eval_densities_host")
+        return V_trg
+
+    def eval_densities_device(self, r_trg, r_src, n_src, F, V_trg=None, digits=-1, stream=None):
+        """The same on torch CUDA tensors on the plan's device (sctl_amd_lists_eval_densities_device), enqueued on `stream` (default:
+        torch's current stream); V_trg of shape (nd, Nt*k1) is accumulated into."""
+        import torch
+        i = self.info
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if F.dim() != 2 or F.shape[1] != self.Ns * i["k0"]:
+            raise SctlAmdError("densities must have shape (nd, %d)" % (self.Ns * i["k0"]))
+        nd = F.shape[0]
+        if V_trg is None or tuple(V_trg.shape) != (nd, self.Nt * i["k1"]):
+            V_trg = torch.zeros((nd, self.Nt * i["k1"]), dtype=tdt, device=r_trg.device)
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        with torch.cuda.device(r_trg.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_lists_eval_densities_device(self._h, nd, _t_ptr(r_trg, tdt, self.Nt * 3, "r_trg"), _t_ptr(r_src, tdt, self.Ns * 3, "r_src"),
+                                                              _t_ptr(n_src, tdt, self.Ns * i["nd"], "n_src"), _t_ptr(F, tdt, nd * self.Ns * i["k0"], "F"),
+                                                              _t_ptr(V_trg, tdt, nd * self.Nt * i["k1"], "V_trg"), digits, cp, cb, C.c_void_p(st.cuda_stream)),
+                   "lists_eval_densities_device")
+        return V_trg
+
     def close(self):
         if getattr(self, "_h", None):
             lib().sctl_amd_lists_destroy(self._h)
@@ -705,3 +745,26 @@ def eval_lists_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_sr
         return plan.eval_host(r_trg, r_src, n_src, v_src, v_trg, digits)
     finally:
         plan.close()
+
+
+def eval_lists_densities_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, F, V_trg=None, digits=-1, ctx=None, device=0):
+    """One-shot sctl_amd_eval_lists_densities_host: F of shape (nd, Ns*SrcDim), returns (nd, Nt*k1)."""
+    info = kernel_info(name)
+    dt = np.dtype(r_trg.dtype)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    F = np.asarray(F)
+    if F.ndim != 2 or F.shape[1] != Ns * info["k0"]:
+        raise SctlAmdError("densities must have shape (nd, %d)" % (Ns * info["k0"]))
+    nd = F.shape[0]
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (trg_off, trg_cnt, src_off, src_cnt)]
+    if len({a.size for a in arrs}) != 1:
+        raise SctlAmdError("the four list arrays must have one entry per list")
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    if V_trg is None or V_trg.shape != (nd, Nt * info["k1"]):
+        V_trg = np.zeros((nd, Nt * info["k1"]), dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    _check(lib().sctl_amd_eval_lists_densities_host(info["id"], _real_of(dt), nd, arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), Nt, Ns,
+                                                    _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                                    _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(F, dt, nd * Ns * info["k0"], "F"),
+                                                    _np_ptr(V_trg, dt, nd * Nt * info["k1"], "V_trg"), digits, cp, cb, device), "eval_lists_densities_host")
+    return V_trg

@@ -2,6 +2,7 @@
 // A plan validates the lists, groups them by target range (a leaf box and ALL the source boxes listed for it become the work of
 // whole waves), orders the work items by cost and keeps them on the device; an evaluation is ONE launch.
 #include "internal.hpp"
+#include "lists_multi_kernel.hpp"
 #include "workspace.hpp"
 
 #include <algorithm>
@@ -285,6 +286,161 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
   if (p->real == SCTL_AMD_F64) { double* o = (double*)v_trg; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
   else { float* o = (float*)v_trg; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
   return SCTL_AMD_OK;
+}
+
+// ---- several densities over the lists (sctl_amd_lists_eval_densities_*, lists_multi_kernel.hpp) ----------------------------------------
+// The plan is the single-density plan: the same handle serves any nd.
+}  // extern "C"
+
+namespace sctl_amd {
+namespace {
+// Launch table of the several-densities list forms: the built-in kernels only; a registered plugin kernel has none (null) and is evaluated one
+// density at a time.
+const ListsMultiEntry* lmulti_entry(int kernel_id) {
+  static const ListsMultiEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &lmulti_Laplace3D_FxU(), &lmulti_Laplace3D_DxU(), &lmulti_Laplace3D_FxdU(),  &lmulti_Stokes3D_FxU(),      &lmulti_Stokes3D_DxU(),
+      &lmulti_Stokes3D_FxT(),  &lmulti_Stokes3D_FSxU(), &lmulti_Stokes3D_FxUP(), &lmulti_Laplace3D_FDxUdU(), &lmulti_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+template <class R> ListsMultiLaunch<R> lmulti_launch(const ListsMultiEntry& me, int mode, int form) {
+  if constexpr (std::is_same<R, double>::value) return me.f64[mode][form];
+  else return me.f32[mode][form];
+}
+// the form for `left` >= 2 densities still to do: the narrowest that takes them all, else the widest; -1: none (the single-density kernel)
+template <class R> int lmulti_form(const ListsMultiEntry* me, int mode, int left) {
+  if (!me || left < 2) return -1;
+  int widest = -1;
+  for (int i = 0; i < kNumListMultiM; i++) {
+    if (!lmulti_launch<R>(*me, mode, i)) continue;
+    if (kListMultiM[i] >= left) return i;
+    widest = i;
+  }
+  return widest;
+}
+
+int check_lists_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  const KernelEntry& k = *p->k;
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  return SCTL_AMD_OK;
+}
+
+// nd >= 2 densities, density-major, on the plan's device: passes of the widest form, then the narrowest form that holds the rest; one density
+// left over (and every density of a plugin kernel) takes the single-density kernel on the same stream.  v is accumulated into.
+template <class R>
+int lists_eval_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits, const void* ctx, int ctx_bytes,
+                           hipStream_t st) {
+  const KernelEntry& k = *p->k;
+  const int64_t f_stride = p->Ns * k.k0, v_stride = p->Nt * k.k1;
+  const ListsMultiEntry* me = lmulti_entry(k.id);
+  const int mode = mode_for(p->real, digits);
+  for (int m0 = 0; m0 < nd;) {
+    const int form = lmulti_form<R>(me, mode, nd - m0);
+    if (form < 0) {
+      const int rc = sctl_amd_lists_eval_device(p, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride, digits, ctx, ctx_bytes, st);
+      if (rc) return rc;
+      m0++;
+      continue;
+    }
+    const int M = kListMultiM[form], nact = nd - m0 < M ? nd - m0 : M;
+    (void)hipGetLastError();
+    ListMultiArgs<R> a{};
+    a.l = ListArgs<R>{{0}, (const ListItem*)p->d_items, (const ListRange*)p->d_ranges, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride,
+                      (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)p->d_groups, (const uint32_t*)p->d_flat};
+    std::memcpy(a.l.xcd_first, p->xcd_first, sizeof a.l.xcd_first);
+    a.f_stride = f_stride; a.v_stride = v_stride; a.nact = nact;
+    lmulti_launch<R>(*me, mode, form)(a, p->nblocks, st);
+    LISTS_TRY(hipGetLastError());
+    count_work(p->pairs * nact, k);
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+}  // namespace
+}  // namespace sctl_amd
+
+extern "C" {
+
+int sctl_amd_lists_eval_densities_device(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, void* v_trg,
+                                         int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const int rc = check_lists_densities(p, nd, ctx, ctx_bytes);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_lists_eval_device(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes, stream);
+  if (nd == 0 || p->nitems == 0) return SCTL_AMD_OK;
+  if (!r_trg || !r_src || !v_src || !v_trg || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
+  DeviceScope scope(p->device);      // the work list lives on the plan's device
+  LISTS_TRY(scope.err);
+  if (p->real == SCTL_AMD_F64)
+    return lists_eval_densities_t<double>(p, nd, (const double*)r_trg, (const double*)r_src, (const double*)n_src, (const double*)v_src, (double*)v_trg, digits,
+                                          ctx, ctx_bytes, (hipStream_t)stream);
+  return lists_eval_densities_t<float>(p, nd, (const float*)r_trg, (const float*)r_src, (const float*)n_src, (const float*)v_src, (float*)v_trg, digits, ctx,
+                                       ctx_bytes, (hipStream_t)stream);
+}
+
+// Coordinates and normals go down once, the nd density rows in one transfer, the nd result rows come back in one; the handle's device buffers
+// and pinned block are the single-density entry's, grown to nd rows on demand.
+int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, void* v_trg,
+                                       int digits, const void* ctx, int ctx_bytes) {
+  const int rc0 = check_lists_densities(p, nd, ctx, ctx_bytes);
+  if (rc0) return rc0;
+  if (nd == 1) return sctl_amd_lists_eval_host(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
+  if (nd == 0 || p->nitems == 0) return SCTL_AMD_OK;
+  const KernelEntry& k = *p->k;
+  if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
+  const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
+  const void* src[4] = {r_trg, r_src, n_src, v_src};
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  size_t total = 0;
+  for (int i = 0; i < 5; i++) {
+    total += Carver::pad(bytes[i]);
+    if (bytes[i] > p->dcap[i]) {
+      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
+      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
+      p->dcap[i] = bytes[i];
+    }
+  }
+  if (total > p->pinned_cap) {
+    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
+    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
+    p->pinned_cap = total;
+  }
+  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
+  const bool same = r_src == r_trg && bytes[0] == bytes[1];
+  Carver cut(p->pinned);
+  for (int i = 0; i < 4; i++) {
+    char* q = cut.take<char>(bytes[i]);
+    if (!bytes[i] || (i == 1 && same)) continue;
+    std::memcpy(q, src[i], bytes[i]);
+    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
+  }
+  LISTS_TRY(hipMemsetAsync(p->dbuf[4], 0, bytes[4], p->st));
+  const int rc = sctl_amd_lists_eval_densities_device(p, nd, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[3], p->dbuf[4], digits, ctx, ctx_bytes,
+                                                      p->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  char* back = cut.take<char>(bytes[4]);
+  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[4], bytes[4], hipMemcpyDeviceToHost, p->st));
+  LISTS_TRY(hipStreamSynchronize(p->st));
+  const int64_t n = (int64_t)nd * p->Nt * k.k1;      // v_trg += device result, every row
+  if (p->real == SCTL_AMD_F64) { double* o = (double*)v_trg; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  else { float* o = (float*)v_trg; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                       const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                       const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device) {
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  sctl_amd_lists* p = nullptr;
+  int rc = sctl_amd_lists_create(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, &p);
+  if (rc != SCTL_AMD_OK) return rc;
+  rc = sctl_amd_lists_eval_densities_host(p, nd, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
+  sctl_amd_lists_destroy(p);
+  return rc;
 }
 
 // one-shot forms: plan, evaluate, release
