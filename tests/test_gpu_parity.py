@@ -296,6 +296,32 @@ def test_kernel_matrix_batch_matches_per_block_oracle(O, name):
     assert rel_l2(b32[5].astype(np.float64), blocks[5]) <= 1e-5
 
 
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("name,Nt", [("Laplace3D-FxU", 70), ("Laplace3D-DxU", 70), ("Stokes3D-FxT", 5)])
+def test_kernel_matrix_with_more_sources_than_grid_rows(O, name, Nt, dt):
+    """matrix_kernel walks the sources with s += gridDim.y and the grid's y stops at 65535: with 65535 + 70 sources the last 70 rows of
+    sources are written by the loop's SECOND step.  Every entry is one pair's value from one instantiation, so those rows (and, for the first
+    step, rows 0 to 69) equal KernelMatrix of the 70 sources alone bit for bit, and meet the oracle."""
+    info = sctl_amd.kernel_info(name)
+    k0 = info["k0"]
+    Ns = 65535 + 70
+    rng = np.random.default_rng(29)
+    xt, xs, xn, _ = _rng_inputs(rng, Nt, Ns, info, dt)
+    xn = xn if info["nd"] else None
+    M = sctl_amd.kernel_matrix_host(name, xt, xs, xn)
+    assert M.shape == (Ns * k0, Nt * info["k1"]) and M.dtype == dt and M.nbytes < 80e6 and np.all(np.isfinite(M))
+    bits = np.int64 if dt == np.float64 else np.int32
+    f8 = lambda a: None if a is None else a.astype(np.float64)
+    for lo, hi in ((Ns - 70, Ns), (0, 70)):
+        xs_p = xs[lo * 3:hi * 3].copy()
+        xn_p = None if xn is None else xn[lo * info["nd"]:hi * info["nd"]].copy()
+        rows = M[lo * k0:hi * k0]
+        alone = sctl_amd.kernel_matrix_host(name, xt, xs_p, xn_p)
+        assert np.array_equal(rows.view(bits), alone.view(bits)), (name, lo, hi)
+        err = rel_l2(rows, O.kernel_matrix(name, f8(xt), f8(xs_p), f8(xn_p)))
+        assert err <= (1e-12 if dt == np.float64 else 1e-5), (name, lo, hi, err)
+
+
 def test_host_entries_are_reentrant(O):
     """The reference calls KernelMatrix inside `omp parallel for` (boundary_integral.txx:949-986) and Eval from whatever thread
     the caller is on: concurrent host-pointer calls from several threads (each gets its own stream, device buffers and pinned

@@ -124,44 +124,67 @@ def test_hip_helmholtz_single_pair_values_against_long_double(k, ns):
 
 
 # ---- per-pair values of the reference's eight kernels (kernel_functions.hpp:15-198) and the fused Laplace kernel through KernelMatrix -------
-def _kernel_values_long_double(name, d, n):
-    """U(d, n)[k0][k1] with the scale factor, in numpy long double, from the formulas of include/sctl/kernel_functions.hpp (cited per kernel)."""
-    L = np.longdouble
+def _kernel_values(name, d, n, L=np.longdouble):
+    """U(d, n)[k0][k1] with the scale factor, from the formulas of include/sctl/kernel_functions.hpp (cited per kernel), every step in the number
+    type L: numpy long double (the truth), or np.float32 (what plain fp32 arithmetic makes of the same formula)."""
     pi = L("3.14159265358979323846264338327950288")
+    pi4, pi8 = L(4) * pi, L(8) * pi
     d = d.astype(L)
     n = None if n is None else n.astype(L)
     r2 = (d * d).sum(-1)
-    ri = 1 / np.sqrt(r2)
-    ri3, ri5 = ri ** 3, ri ** 5
+    ri = L(1) / np.sqrt(r2)
+    ri3 = ri * ri * ri
+    ri5 = ri3 * ri * ri
     P = d.shape[0]
     eye = np.eye(3, dtype=L)
     if name == "Laplace3D-FxU":      # :26-30
-        return (ri / (4 * pi)).reshape(P, 1, 1)
+        return (ri / pi4).reshape(P, 1, 1)
     if name == "Laplace3D-DxU":      # :44-50
-        return ((d * n).sum(-1) * ri3 / (4 * pi)).reshape(P, 1, 1)
+        return ((d * n).sum(-1) * ri3 / pi4).reshape(P, 1, 1)
     if name == "Laplace3D-FxdU":     # :64-71, scale -1/(4 pi)
-        return (-(d * ri3[:, None]) / (4 * pi)).reshape(P, 1, 3)
-    stokeslet = (eye[None] * ri[:, None, None] + d[:, :, None] * d[:, None, :] * ri3[:, None, None]) / (8 * pi)
+        return (-(d * ri3[:, None]) / pi4).reshape(P, 1, 3)
+    stokeslet = (eye[None] * ri[:, None, None] + d[:, :, None] * d[:, None, :] * ri3[:, None, None]) / pi8
     if name == "Stokes3D-FxU":       # :85-94
         return stokeslet
     if name == "Stokes3D-DxU":       # :108-119, scale 3/(4 pi)
-        return d[:, :, None] * d[:, None, :] * ((d * n).sum(-1) * ri5)[:, None, None] * 3 / (4 * pi)
+        return d[:, :, None] * d[:, None, :] * ((d * n).sum(-1) * ri5)[:, None, None] * (L(3) / pi4)
     if name == "Stokes3D-FxT":       # :133-145, scale -3/(4 pi): u[i][j*3+k] = r_i r_j r_k / r^5
         t = d[:, :, None, None] * d[:, None, :, None] * d[:, None, None, :] * ri5[:, None, None, None]
-        return (-3 / (4 * pi) * t).reshape(P, 3, 9)
+        return (-(L(3) / pi4) * t).reshape(P, 3, 9)
     if name == "Stokes3D-FSxU":      # :159-171: rows 0-2 the Stokeslet, row 3 the source/sink r_j / r^3
-        return np.concatenate([stokeslet, (d * ri3[:, None] / (8 * pi))[:, None, :]], axis=1)
+        return np.concatenate([stokeslet, (d * ri3[:, None] / pi8)[:, None, :]], axis=1)
     if name == "Stokes3D-FxUP":      # :185-197: columns 0-2 the Stokeslet, column 3 the pressure r_i / r^3
-        return np.concatenate([stokeslet, (d * ri3[:, None] / (8 * pi))[:, :, None]], axis=2)
+        return np.concatenate([stokeslet, (d * ri3[:, None] / pi8)[:, :, None]], axis=2)
     if name == "Laplace3D-FDxUdU":   # rows (q, mu) -> columns (u, grad u): q/r + mu (r.n)/r^3 and its gradient in the target
         rn = (d * n).sum(-1)
         U = np.zeros((P, 2, 4), dtype=L)
         U[:, 0, 0] = ri
         U[:, 0, 1:] = -d * ri3[:, None]
         U[:, 1, 0] = rn * ri3
-        U[:, 1, 1:] = n * ri3[:, None] - 3 * d * (rn * ri5)[:, None]
-        return U / (4 * pi)
+        U[:, 1, 1:] = n * ri3[:, None] - L(3) * d * (rn * ri5)[:, None]
+        return U / pi4
     raise ValueError(name)
+
+
+def _per_pair_error(name, got, ref, d, nn):
+    """Relative error of each pair's K0 x K1 block (Frobenius norm) against the long-double block `ref`."""
+    den = (ref ** 2).sum((1, 2))
+    if name in ("Laplace3D-DxU", "Stokes3D-DxU"):         # values proportional to r.n vanish for r perpendicular to n: measure against |r| |n| instead
+        L = np.longdouble
+        dl, nl = d.astype(L), nn.astype(L)
+        den = den * ((dl * dl).sum(-1) * (nl * nl).sum(-1)) / ((dl * nl).sum(-1) ** 2)
+    return np.sqrt((((got - ref) ** 2).sum((1, 2)) / den).astype(np.float64))
+
+
+def _pair_cloud(info, dt):
+    """700 targets x 300 sources in [0,1)^3, 50 of the sources within 1e-3 of the origin (pairs at 1e3 : 1 distance ratios), rounded to dt."""
+    rng = np.random.default_rng(11)
+    Nt, Ns = 700, 300
+    xt = rng.random((Nt, 3)) * np.array([1.0, 1.0, 1.0])
+    xs = rng.random((Ns, 3))
+    xs[:50] *= 1e-3
+    xn = rng.random((Ns, 3)) - 0.5 if info["nd"] else None
+    return xt.astype(dt), xs.astype(dt), None if xn is None else xn.astype(dt)
 
 
 _POWERS = {"Laplace3D-FxU": 1, "Laplace3D-DxU": 3, "Laplace3D-FxdU": 3, "Stokes3D-FxU": 3, "Stokes3D-DxU": 5, "Stokes3D-FxT": 5, "Stokes3D-FSxU": 3,
@@ -177,25 +200,47 @@ def test_hip_kernel_values_one_pair_at_a_time_against_long_double(name, digits):
     sources would average their errors away: full precision within a few ulp per power of 1/r, 10 digits within its stated 4.3e-15 per power."""
     import sctl_amd
     info = sctl_amd.kernel_info(name)
-    rng = np.random.default_rng(11)
-    Nt, Ns = 700, 300
-    xt = rng.random((Nt, 3)) * np.array([1.0, 1.0, 1.0])
-    xs = rng.random((Ns, 3))
-    xs[:50] *= 1e-3                                        # some pairs at 1e3 : 1 distance ratios
-    xn = rng.random((Ns, 3)) - 0.5 if info["nd"] else None
+    xt, xs, xn = _pair_cloud(info, np.float64)
+    Nt, Ns = xt.shape[0], xs.shape[0]
     M = sctl_amd.kernel_matrix_host(name, xt.ravel().copy(), xs.ravel().copy(), None if xn is None else xn.ravel().copy(), digits=digits)
     k0, k1 = info["k0"], info["k1"]
     got = M.reshape(Ns, k0, Nt, k1).transpose(0, 2, 1, 3).reshape(Ns * Nt, k0, k1)
     d = (xt[None, :, :] - xs[:, None, :]).reshape(-1, 3)  # exactly the double subtraction the kernel does
     nn = None if xn is None else np.repeat(xn, Nt, axis=0)
-    ref = _kernel_values_long_double(name, d, nn)
-    den = (ref ** 2).sum((1, 2))
-    if name in ("Laplace3D-DxU", "Stokes3D-DxU"):         # values proportional to r.n vanish for r perpendicular to n: measure against |r| |n| instead
-        L = np.longdouble
-        dl, nl = d.astype(L), nn.astype(L)
-        den = den * ((dl * dl).sum(-1) * (nl * nl).sum(-1)) / ((dl * nl).sum(-1) ** 2)
-    err = np.sqrt((((got - ref) ** 2).sum((1, 2)) / den).astype(np.float64))
+    err = _per_pair_error(name, got, _kernel_values(name, d, nn), d, nn)
     p = _POWERS[name]
     bound = (0.5e-15 + 0.5e-15 * p) if digits < 0 else 5e-15 * p
     # measured on MI355X (round 3), max over the 210 000 pairs: full precision 4.8e-16 (Laplace SL) ... 1.8e-15 (fused Laplace); 10 digits 3.8e-15 ... 2.1e-14
     assert err.max() <= bound, (name, digits, err.max(), bound)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("digits", [-1, 9])
+@pytest.mark.parametrize("name", sorted(_POWERS))
+def test_hip_fp32_kernel_values_one_pair_at_a_time_against_long_double(name, digits):
+    """The same pair-by-pair check for fp32 KernelMatrix at both fp32 accuracies (digits -1: the hardware reciprocal square root as it comes;
+    9: one Newton step), on the same cloud rounded to fp32.  The bound is not fitted to the kernel: the formula is evaluated step by step in
+    np.float32 (correctly rounded sqrt and divide) on the same pairs, its largest per-pair error against long double is taken, and the kernel is
+    allowed 4 times that: its reciprocal square root is the hardware's approximate one, and it builds the powers of 1/r with up to p more
+    multiplications than the formula written out."""
+    import sctl_amd
+    info = sctl_amd.kernel_info(name)
+    xt, xs, xn = _pair_cloud(info, np.float32)
+    Nt, Ns = xt.shape[0], xs.shape[0]
+    M = sctl_amd.kernel_matrix_host(name, xt.ravel().copy(), xs.ravel().copy(), None if xn is None else xn.ravel().copy(), digits=digits)
+    assert M.dtype == np.float32
+    k0, k1 = info["k0"], info["k1"]
+    got = M.reshape(Ns, k0, Nt, k1).transpose(0, 2, 1, 3).reshape(Ns * Nt, k0, k1)
+    d = (xt[None, :, :] - xs[:, None, :]).reshape(-1, 3)  # exactly the float subtraction the kernel does
+    assert d.dtype == np.float32
+    nn = None if xn is None else np.repeat(xn, Nt, axis=0)
+    ref = _kernel_values(name, d, nn)
+    plain = _kernel_values(name, d, nn, np.float32)
+    assert plain.dtype == np.float32
+    err, err_plain = _per_pair_error(name, got, ref, d, nn), _per_pair_error(name, plain, ref, d, nn)
+    print("%s digits %d: kernel %.3e, plain fp32 formula %.3e" % (name, digits, err.max(), err_plain.max()))
+    # measured, max over the 210 000 pairs: plain np.float32 formula | kernel on MI355X at digits -1 | at digits 9
+    #   Laplace3D-FxU 2.09e-7 | 1.96e-7 | 2.07e-7     Laplace3D-DxU 5.02e-7 | 4.57e-7 | 5.10e-7     Laplace3D-FxdU 5.21e-7 | 4.67e-7 | 5.21e-7
+    #   Laplace3D-FDxUdU 8.65e-7 | 7.91e-7 | 8.52e-7  Stokes3D-FxU 3.07e-7 | 2.87e-7 | 3.14e-7      Stokes3D-DxU 6.86e-7 | 6.41e-7 | 6.90e-7
+    #   Stokes3D-FxT 7.61e-7 | 7.13e-7 | 8.95e-7      Stokes3D-FSxU 4.29e-7 | 4.06e-7 | 4.36e-7     Stokes3D-FxUP 4.29e-7 | 4.06e-7 | 4.36e-7
+    assert err.max() <= 4 * err_plain.max(), (name, digits, err.max(), err_plain.max())
