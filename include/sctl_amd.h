@@ -94,7 +94,7 @@ int sctl_amd_num_kernels(void);                 /* built-in + registered: valid 
  * make_entry<Ker>() builds (function pointers into the plugin's own code object); abi_version and desc_bytes guard against a
  * plugin compiled with other device headers.  Returns the new kernel id (>= SCTL_AMD_NUM_KERNELS) or a negative error code
  * (a name that is already registered is refused).  Registered kernels live until the process ends. */
-#define SCTL_AMD_DEVICE_ABI 3
+#define SCTL_AMD_DEVICE_ABI 4
 typedef struct sctl_amd_kernel_desc {
   int abi_version;          /* SCTL_AMD_DEVICE_ABI of the headers the plugin was compiled with */
   int desc_bytes;           /* sizeof(sctl_amd_kernel_desc) */
@@ -213,6 +213,25 @@ int sctl_amd_op_eval_densities(sctl_amd_op* op, int nd, const void* v_src, void*
  * into several launches rather than take fewer source splits than the L2 rule asks for.  nd == 1 is sctl_amd_eval_plan's answer. */
 int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* densities_per_pass, int* passes,
                                  int* trg_per_lane, int* src_splits, int64_t* workgroups, int64_t* workspace_bytes);
+
+/* ---- the transposed sum: g_src += A^T w_trg ------------------------------------------------------------------------------------ */
+/* With A the operator sctl_amd_eval_* applies, v_trg = A v_src, these entries apply its transpose to a vector of TARGET weights:
+ *     g_src[s*SrcDim + k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] * w_trg[t*TrgDim + k1]
+ * i.e. KernelMatrix (generic-kernel.txx:191-307, (Ns*SrcDim) x (Nt*TrgDim)) times w_trg, without the matrix: the adjoint a BiCG / QMR /
+ * LSQR iteration, an adjoint solve or a norm estimate needs, and the gradient of <w, A v_src> with respect to v_src.  The normals stay
+ * with the sources, a coincident pair contributes 0, and `digits`, `ctx` and every argument check are those of the forward entries; a
+ * registered kernel whose functor has no transposed form (no pair_t: device/kernel_plugin.hpp) is SCTL_AMD_ERR_UNKNOWN_KERNEL here and
+ * evaluates forward as before.  The exact all-pairs kernel on one device (device/eval_transpose_kernel.hpp): sums in a fixed order,
+ * bit-reproducible.  Counters grow by Nt*Ns pairs.  Nt == 0 or Ns == 0: nothing is read or written. */
+/* DEVICE arrays; enqueued on `stream`; g_src (Ns*SrcDim values) is accumulated into. */
+int sctl_amd_eval_transpose_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                   const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream);
+/* HOST arrays, one device; returns when g_src is final.  accumulate != 0 adds to g_src, 0 overwrites it. */
+int sctl_amd_eval_transpose_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                 const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes, int device);
+/* The plan of such a call (no side effects, no GPU needed): sources per lane, splits of the target range, and the bytes of partial sums
+ * of one launch.  Those stay within 2 GB: the sources are cut into several launches rather than the targets into fewer splits. */
+int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* src_per_lane, int* splits, int64_t* workspace_bytes);
 
 /* ---- rank-parallel evaluation: one process per GPU (ParticleFMM::EvalDirect under MPI, fmm-wrapper.txx:504-561) --------------- */
 /* The reference partitions targets and sources over MPI ranks and rotates the source blocks round a ring (:537-558).  Here every

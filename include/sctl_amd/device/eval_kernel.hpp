@@ -49,6 +49,8 @@ template <> __device__ __forceinline__ float max_finite<float>() { return 3.4028
 __device__ __forceinline__ double fabs_(double x) { return __builtin_fabs(x); }
 __device__ __forceinline__ float fabs_(float x) { return __builtin_fabsf(x); }
 
+// eval_transpose_kernel (eval_transpose_kernel.hpp) is this kernel's twin with the roles of the point sets exchanged: the XCD mapping, the prefetch,
+// the speculation and its repair, the variant dispatch and the store are the same there, so a fix to any of them here belongs there too.
 template <class Ker, class R, int MODE, int T>
 __global__ void __launch_bounds__(kBlock) eval_kernel(const EvalArgs<R> a) {
   constexpr int K0 = Ker::K0, K1 = Ker::K1, ND = Ker::ND, NREC = Ker::NREC;

@@ -32,6 +32,16 @@
 // (rsqrt_scaled_factor(mode, p) for terms in r^-p) and the library divides the scale by it; `template <class R, int MODE> pack_mode(rec, x, n, f)`
 // replaces pack() when the record depends on the mode (a density kept pre-multiplied by rsqrt_scaled_c2(MODE): Stokes3D_FxU), and
 // `template <class R, int MODE> finish_mode(acc)` replaces finish() (outputs that accumulate different powers: Laplace3D_FDxUdU).
+// Optional, the TRANSPOSED form (sctl_amd_eval_transpose_*: g[s,k0] += sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] w[t,k1]; the source owns the output and its
+// normal, the targets stream through LDS).  A functor that supplies all of
+//     static constexpr int NREC_T = ...;                      // reals per streamed TARGET record (x, y, z first, then what the pair needs of w[K1])
+//     template <class R> static __device__ void pack_t(R* rec, const R* x_trg, const R* w);      // or pack_t_mode<R, MODE>, as pack_mode
+//     template <class R, int MODE, bool MASKED>
+//     static __device__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const sctl_amd::KerCtx& ctx, const Consts<R>& K);
+// gets the transposed entries: acc[k0] += sum_k1 U(d, n)[k0][k1] w[k1] with the SAME d = x_trg - x_src as pair() and n the source's normal (from
+// registers; unused R[1] when ND == 0), the same masking rule, accuracy modes and acc_factor(mode) as pair().  `finish_t<R>(R (&acc)[K0])` /
+// `finish_t_mode<R, MODE>` are the optional counterparts of finish / finish_mode.  Without pair_t the kernel registers and runs as before and
+// the transposed entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for it (tests/plugin/yukawa_kernel.hip has none, yukawa_t_kernel.hip has one).
 // A kernel with per-launch constants of its own supplies a Consts type instead of DefaultConsts: it is built once per workgroup from
 // (double* lds) or, when it has such a constructor, from (double* lds, const KerCtx& ctx) — e.g. to derive scalar-register constants
 // from a wavenumber (ukernels.hpp: HelmholtzConsts) — and handed to every pair() call.

@@ -2,6 +2,7 @@
 // ~200 kernel instantiations compile in parallel.  capi.hip only sees function pointers.
 #pragma once
 #include "eval_kernel.hpp"
+#include "eval_transpose_kernel.hpp"
 #include "lists_kernel.hpp"
 
 namespace sctl_amd {
@@ -9,8 +10,11 @@ namespace sctl_amd {
 constexpr int kNumT = 3;                       // targets per lane: 1, 2, 4
 constexpr int kTvalues[kNumT] = {1, 2, 4};
 constexpr int kNumMode = 3;                    // rsqrt refinement: seed, Newton, Halley (ukernels.hpp)
+constexpr int kNumTT = 2;                      // sources per lane of the transposed evaluator: 1, 2
+constexpr int kTTvalues[kNumTT] = {1, 2};
 
 template <class R> using EvalLaunch = void (*)(const EvalArgs<R>&, dim3 grid, hipStream_t);
+template <class R> using EvalTLaunch = void (*)(const EvalTArgs<R>&, dim3 grid, hipStream_t);
 template <class R> using MatrixBatchLaunch = void (*)(const MatTile* tiles, int64_t ntiles, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, hipStream_t);
 template <class R> using ListsLaunch = void (*)(const ListArgs<R>&, int64_t nblocks, hipStream_t);
 template <class R> using MatrixLaunch = void (*)(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, dim3 grid, hipStream_t);
@@ -28,10 +32,17 @@ struct KernelEntry {
   MatrixBatchLaunch<float> matrix_batch_f32[kNumMode];
   ListsLaunch<double> lists_f64[kNumMode];          // lists_kernel.hpp
   ListsLaunch<float> lists_f32[kNumMode];
+  // the transposed evaluator (eval_transpose_kernel.hpp): all null, and nrec_t 0, for a functor without pair_t
+  int nrec_t;
+  EvalTLaunch<double> eval_t_f64[kNumMode][kNumTT];
+  EvalTLaunch<float> eval_t_f32[kNumMode][kNumTT];  // modes 0 and 1 only (mode 2 aliases mode 1)
 };
 
 template <class Ker, class R, int MODE, int T> void launch_eval(const EvalArgs<R>& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL((eval_kernel<Ker, R, MODE, T>), grid, dim3(kBlock), 0, st, a);
+}
+template <class Ker, class R, int MODE, int T> void launch_eval_t(const EvalTArgs<R>& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((eval_transpose_kernel<Ker, R, MODE, T>), grid, dim3(kBlock), 0, st, a);
 }
 template <class Ker, class R, int MODE> void launch_matrix(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, R* M, R scale,
                                                            const KerCtx& ctx, dim3 grid, hipStream_t st) {
@@ -65,8 +76,39 @@ template <class Ker> KernelEntry make_entry(int ctx_bytes) {
   e.matrix_batch_f32[2] = launch_matrix_batch<Ker, float, 1>;
   e.lists_f64[0] = launch_lists<Ker, double, 0>; e.lists_f64[1] = launch_lists<Ker, double, 1>; e.lists_f64[2] = launch_lists<Ker, double, 2>;
   e.lists_f32[0] = launch_lists<Ker, float, 0>; e.lists_f32[1] = launch_lists<Ker, float, 1>; e.lists_f32[2] = launch_lists<Ker, float, 1>;
+  if constexpr (HasPairT<Ker>::value) {
+    e.nrec_t = Ker::NREC_T;
+#define SCTL_AMD_ROW_T(R, arr, M, MM) arr[M][0] = launch_eval_t<Ker, R, MM, 1>; arr[M][1] = launch_eval_t<Ker, R, MM, 2>;
+    SCTL_AMD_ROW_T(double, e.eval_t_f64, 0, 0) SCTL_AMD_ROW_T(double, e.eval_t_f64, 1, 1) SCTL_AMD_ROW_T(double, e.eval_t_f64, 2, 2)
+    SCTL_AMD_ROW_T(float, e.eval_t_f32, 0, 0) SCTL_AMD_ROW_T(float, e.eval_t_f32, 1, 1) SCTL_AMD_ROW_T(float, e.eval_t_f32, 2, 1)
+#undef SCTL_AMD_ROW_T
+  }
   return e;
 }
+
+// The transposed launchers of the ten built-in functors are compiled in units of their own (inst_t_*.hip): make_entry, in inst_*.hip, only takes
+// their addresses.  A plugin's functor is instantiated where its make_entry is.
+#define SCTL_AMD_EVAL_T_INSTANCES(PREFIX, Ker)                                                              \
+  PREFIX template void launch_eval_t<Ker, double, 0, 1>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, double, 0, 2>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, double, 1, 1>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, double, 1, 2>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, double, 2, 1>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, double, 2, 2>(const EvalTArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_t<Ker, float, 0, 1>(const EvalTArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_t<Ker, float, 0, 2>(const EvalTArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_t<Ker, float, 1, 1>(const EvalTArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_t<Ker, float, 1, 2>(const EvalTArgs<float>&, dim3, hipStream_t);
+SCTL_AMD_EVAL_T_INSTANCES(extern, Laplace3D_FxU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Laplace3D_DxU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Laplace3D_FxdU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FxU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_DxU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FxT)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FSxU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FxUP)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Laplace3D_FDxUdU)
+SCTL_AMD_EVAL_T_INSTANCES(extern, Helmholtz3D_FxU)
 
 // defined in inst_*.hip
 const KernelEntry& entry_Laplace3D_FxU();

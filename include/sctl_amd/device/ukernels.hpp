@@ -20,6 +20,13 @@
 //   pair_m<R,MODE,MASKED,M>(acc, d, rec, ctx, K)   acc[M][K1]: the density-independent factors of the pair (distance, reciprocal square root
 //                              and its refinement, Helmholtz's e^{ikr}) once, then one contraction per density.  Same masking and acc_factor
 //                              as pair(): a launch scales both forms alike.
+// and the transposed forms used by eval_transpose_kernel.hpp (g[s,k0] += sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] w[t,k1]: the SOURCE owns the output and
+// its normal, the TARGETS stream):
+//   NREC_T                     reals per streamed target record: the coordinates, then what the pair needs of w[K1]
+//   pack_t<R>(rec, x_t, w)     or pack_t_mode<R,MODE> where the record depends on the accuracy mode, as pack_mode does
+//   pair_t<R,MODE,MASKED[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[k0] += sum_k1 U(d, n)[k0][k1] w[k1] with the SAME d = x_trg - x_src as pair(), n the owner's
+//                              normal (R[3], or R[1] unused when ND == 0) from registers.  Same rsqrt helpers, modes, masking and acc_factor as pair().
+//   finish_t<R>(acc) / finish_t_mode<R,MODE>(acc)   optional, applied once to a source's K0 sums (FinishTOf)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -200,6 +207,28 @@ template <class Ker, class R, int MODE> struct PackOf<Ker, R, MODE, std::void_t<
 };
 template <class Ker, class R, int MODE> __device__ __forceinline__ void pack_record(R* rec, const R* x, const R* n, const R* f) { PackOf<Ker, R, MODE>::apply(rec, x, n, f); }
 
+// The transposed form of a kernel (pair_t and its record) is optional: a functor without it evaluates A only.  HasPairT detects the streamed record's size,
+// which every transposed form must name; PackTOf / FinishTOf pick pack_t or pack_t_mode and the optional finish_t / finish_t_mode as PackOf / FinishOf do.
+template <class Ker, class = void> struct HasPairT : std::false_type {};
+template <class Ker> struct HasPairT<Ker, std::void_t<decltype(Ker::NREC_T), decltype(&Ker::template pair_t<double, 0, true>)>> : std::true_type {};
+template <class Ker, class R, int MODE, class = void> struct PackTOf {
+  static __device__ __forceinline__ void apply(R* rec, const R* x, const R* w) { Ker::template pack_t<R>(rec, x, w); }
+};
+template <class Ker, class R, int MODE> struct PackTOf<Ker, R, MODE, std::void_t<decltype(&Ker::template pack_t_mode<R, MODE>)>> {
+  static __device__ __forceinline__ void apply(R* rec, const R* x, const R* w) { Ker::template pack_t_mode<R, MODE>(rec, x, w); }
+};
+template <class Ker, class R, int MODE> __device__ __forceinline__ void pack_t_record(R* rec, const R* x, const R* w) { PackTOf<Ker, R, MODE>::apply(rec, x, w); }
+template <class Ker, class R, int MODE, class = void, class = void> struct FinishTOf {
+  static __device__ __forceinline__ void apply(R (&)[Ker::K0]) {}
+};
+template <class Ker, class R, int MODE, class V> struct FinishTOf<Ker, R, MODE, std::void_t<decltype(&Ker::template finish_t<R>)>, V> {
+  static __device__ __forceinline__ void apply(R (&acc)[Ker::K0]) { Ker::template finish_t<R>(acc); }
+};
+template <class Ker, class R, int MODE> struct FinishTOf<Ker, R, MODE, void, std::void_t<decltype(&Ker::template finish_t_mode<R, MODE>)>> {
+  static __device__ __forceinline__ void apply(R (&acc)[Ker::K0]) { Ker::template finish_t_mode<R, MODE>(acc); }
+};
+template <class Ker, class R, int MODE> __device__ __forceinline__ void finish_t_acc(R (&acc)[Ker::K0]) { FinishTOf<Ker, R, MODE>::apply(acc); }
+
 // Per-kernel constants of a launch: Consts(lds, capacity, ctx) when the type takes the scratch capacity (in doubles) and the context,
 // Consts(lds, ctx) when it takes the context, Consts(lds) otherwise.
 template <class KC> __device__ __forceinline__ KC make_consts(double* lds, int lds_doubles, const KerCtx& ctx) {
@@ -371,6 +400,12 @@ struct Laplace3D_FxU {
 #pragma unroll
     for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[3 + m], rinv, acc[m][0]);
   }
+  // transposed: the kernel is symmetric, g += w / r; record x_t, w
+  static constexpr int NREC_T = 4;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) { rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    acc[0] = fma_(rec[3], rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq), acc[0]);
+  }
 };
 
 // ---- Laplace double layer: u = (r.n) f / r^3   (kernel_functions.hpp:33-51); record holds n*f ------------
@@ -392,6 +427,13 @@ struct Laplace3D_DxU {
     const R t = dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq);
 #pragma unroll
     for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[6 + m], t, acc[m][0]);
+  }
+  // transposed: g += (d.n) w / r^3 with the owner's n in registers: nothing of the pair can be pre-multiplied into the record, so w costs one
+  // multiplication more than the forward pair's n f; record x_t, w
+  static constexpr int NREC_T = 4;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) { rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    acc[0] = fma_(dot3(d, n), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq) * rec[3], acc[0]);
   }
 };
 
@@ -418,6 +460,14 @@ struct Laplace3D_FxdU {
     for (int m = 0; m < M; m++)
 #pragma unroll
       for (int j = 0; j < 3; j++) acc[m][j] = fma_(rec[3 + m], td[j], acc[m][j]);
+  }
+  // transposed: g += (d.w) / r^3, one dot product and one FMA; record x_t, w[3]
+  static constexpr int NREC_T = 6;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) {
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; rec[4] = w[1]; rec[5] = w[2];
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    acc[0] = fma_(dot3(d, rec + 3), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq), acc[0]);
   }
 };
 
@@ -454,6 +504,12 @@ struct Stokes3D_FxU {
       for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
     }
   }
+  // transposed: the block is symmetric, g = w / r + (d.w) d / r^3: the forward record and pair with w for f
+  static constexpr int NREC_T = NREC;
+  template <class R, int MODE> static __device__ __forceinline__ void pack_t_mode(R* rec, const R* x, const R* w) { pack_mode<R, MODE>(rec, x, nullptr, w); }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    pair<R, MODE, MASKED>(acc, d, rec, KerCtx{}, K);
+  }
 };
 
 // ---- stresslet: u_j = r_j (r.f)(r.n) / r^5, scale 3/(4 pi)   (kernel_functions.hpp:97-120) ----------------
@@ -482,6 +538,15 @@ struct Stokes3D_DxU {
 #pragma unroll
       for (int j = 0; j < 3; j++) acc[m][j] = fma_(gd[j], rf, acc[m][j]);
     }
+  }
+  // transposed: g_i += d_i (d.w)(d.n) / r^5, the forward pair with the owner's n from registers; record x_t, w[3]
+  static constexpr int NREC_T = 6;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) {
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; rec[4] = w[1]; rec[5] = w[2];
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R t = dot3(d, n) * dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
   }
 };
 
@@ -525,6 +590,21 @@ struct Stokes3D_FxT {
     }
   }
   template <class R> static __device__ __forceinline__ void finish(R (&acc)[K1]) { acc[3] = acc[1]; acc[6] = acc[2]; acc[7] = acc[5]; }
+  // transposed: g_i += d_i (d^T W d) / r^5 for the full 3 x 3 weight W = w[j*3+k] (no symmetry assumed).  Only the symmetric part of W enters the
+  // quadratic form, so the record holds S = the diagonal and the sums W_jk + W_kj (j < k): d^T W d in 9 instructions where the nine entries take 12.
+  // record x_t, S00 S01 S02 S11 S12 S22
+  static constexpr int NREC_T = 10;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) {
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2];
+    rec[3] = w[0]; rec[4] = w[1] + w[3]; rec[5] = w[2] + w[6]; rec[6] = w[4]; rec[7] = w[5] + w[7]; rec[8] = w[8]; rec[9] = 0;
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R a0 = fma_(rec[5], d[2], fma_(rec[4], d[1], rec[3] * d[0]));
+    const R a1 = fma_(rec[7], d[2], rec[6] * d[1]);
+    const R q = fma_(d[2] * rec[8], d[2], fma_(a1, d[1], a0 * d[0]));
+    const R t = q * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
+  }
 };
 
 // ---- Stokeslet + source/sink: u_j = f_j / r + ((r.f) + f_3) r_j / r^3   (kernel_functions.hpp:148-172) ------
@@ -558,6 +638,19 @@ struct Stokes3D_FSxU {
 #pragma unroll
       for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
     }
+  }
+  // transposed: three Stokeslet rows g_i += w_i / r + (d.w) d_i / r^3 and g_3 += (d.w) / r^3 — the velocity + pressure kernel's forward arithmetic
+  // record x_t, w (for the dot product), C^2 w
+  static constexpr int NREC_T = 10;
+  template <class R, int MODE> static __device__ __forceinline__ void pack_t_mode(R* rec, const R* x, const R* w) {
+    const R c2 = R(rsqrt_scaled_c2(MODE));
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; rec[4] = w[1]; rec[5] = w[2]; rec[6] = c2 * w[0]; rec[7] = c2 * w[1]; rec[8] = c2 * w[2]; rec[9] = 0;
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
+    const R t = dot3(d, rec + 3) * (y * y);
+    for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[6 + j]), acc[j]);
+    acc[3] = fma_(t, y, acc[3]);
   }
 };
 
@@ -594,6 +687,18 @@ struct Stokes3D_FxUP {
       for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], rf, fma_(yc, f[j], acc[m][j]));
       acc[m][3] = fma_(y3, rf, acc[m][3]);
     }
+  }
+  // transposed: g_i += w_i / r + ((d.w_u) + w_p) d_i / r^3, the Stokeslet of the velocity weights plus d w_p / r^3 — the source/sink kernel's
+  // forward arithmetic.  record x_t, w_u, w_p, C^2 w_u
+  static constexpr int NREC_T = 10;
+  template <class R, int MODE> static __device__ __forceinline__ void pack_t_mode(R* rec, const R* x, const R* w) {
+    const R c2 = R(rsqrt_scaled_c2(MODE));
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; rec[4] = w[1]; rec[5] = w[2]; rec[6] = w[3]; rec[7] = c2 * w[0]; rec[8] = c2 * w[1]; rec[9] = c2 * w[2];
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
+    const R t = fma_(d[2], rec[5], fma_(d[1], rec[4], fma_(d[0], rec[3], rec[6]))) * (y * y);
+    for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[7 + j]), acc[j]);
   }
 };
 
@@ -656,6 +761,27 @@ struct Laplace3D_FDxUdU {
     }
   }
   template <class R, int MODE> static __device__ __forceinline__ void finish_mode(R (&acc)[K1]) { acc[0] *= R(rsqrt_scaled_c2(MODE)); }
+  // transposed: two outputs from four weights (w_u, w_g).  With y = C / r, A = C^2 (d.w_g) / r^2 and dn = d.n
+  //   g_q  += y (C^2 w_u - A)                                      C^3 x its value: finish_t_mode multiplies by C^2, as finish_mode does for the potential
+  //   g_mu += y^3 (dn (C^2 w_u - 3 A) + C^2 (n.w_g))               C^5 x its value
+  // record x_t, C^2 w_u, w_g (for d.w_g), C^2 w_g (for n.w_g)
+  static constexpr int NREC_T = 10;
+  template <class R, int MODE> static __device__ __forceinline__ void pack_t_mode(R* rec, const R* x, const R* w) {
+    const R c2 = R(rsqrt_scaled_c2(MODE));
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = c2 * w[0];
+    rec[4] = w[1]; rec[5] = w[2]; rec[6] = w[3]; rec[7] = c2 * w[1]; rec[8] = c2 * w[2]; rec[9] = c2 * w[3];
+  }
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);   // C / r
+    const R y2 = y * y;
+    const R y3 = y2 * y;
+    const R a = dot3(d, rec + 4) * y2;                      // C^2 (d.w_g) / r^2
+    acc[0] = fma_(y, rec[3] - a, acc[0]);
+    const R e = fma_(-a, K.c3, rec[3]);                     // C^2 (w_u - 3 (d.w_g) / r^2)
+    const R h = fma_(n[2], rec[9], fma_(n[1], rec[8], fma_(n[0], rec[7], dot3(d, n) * e)));
+    acc[1] = fma_(y3, h, acc[1]);
+  }
+  template <class R, int MODE> static __device__ __forceinline__ void finish_t_mode(R (&acc)[K0]) { acc[0] *= R(rsqrt_scaled_c2(MODE)); }
 };
 
 static_assert(helmholtz_dist_factor(2) == rsqrt_scaled_factor(2, 1) && helmholtz_dist_factor(0) == 1, "HelmholtzConsts' distance factor is the cubic step's A");
@@ -716,6 +842,33 @@ struct Helmholtz3D_FxU {
       acc[m][0] = fma_(gr, fr, fma_(-gi, fi, acc[m][0]));
       acc[m][1] = fma_(gi, fr, fma_(gr, fi, acc[m][1]));
     }
+  }
+  // transposed: the same G = e^{ikr} / r from the same tables and variants; the 2 x 2 block [[gr, gi], [-gi, gr]] changes the sign of its off-diagonal:
+  // g_re += gr w_re + gi w_im, g_im += gr w_im - gi w_re (the real 2 x 2 block transposed, i.e. conj(G) w as complex numbers: G itself is not conjugated,
+  // only the roles of its imaginary part change).
+  // record x_t, w_re, w_im
+  static constexpr int NREC_T = 6;
+  template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) {
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; rec[4] = w[1]; rec[5] = 0;
+  }
+  template <class R, int MODE, bool MASKED, int VARIANT = 0> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&)[1], const R* rec, const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+    acc[0] = fma_(gr, rec[3], fma_(gi, rec[4], acc[0]));
+    acc[1] = fma_(gr, rec[4], fma_(-gi, rec[3], acc[1]));
   }
   // fp64, one reduction of r for the whole factor e^{ikr} (fastmath.hpp: cexp_tab_k); returns G = e^{ikr} / r.  The speculative pass runs it
   // unconditionally and records the largest distance; the careful pass branches per pair to libm beyond the table's range.

@@ -186,6 +186,26 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_densities_host");
   }
 
+  // The transposed sum (sctl_amd_eval_transpose_host; not in the reference, whose only route to A^T is KernelMatrix and a product):
+  //   g_src[s*SrcDim + k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] * w_trg[t*TrgDim + k1],
+  // KernelMatrix's M times w_trg without M.  g_src follows Eval's rule: the right size (Ns*SrcDim) is accumulated into, any other is resized and zeroed.
+  template <class Real, Integer digits = -1>
+  void EvalTranspose(Vector<Real>& g_src, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Vector<Real>& w_trg) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM;
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(w_trg.Dim() == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    if (g_src.Dim() != Ns * KDIM0) {
+      g_src.ReInit(Ns * KDIM0);
+      g_src.SetZero();
+    }
+    RequireSupported();
+    const int rc = sctl_amd_eval_transpose_host(DeviceKernelId(), RealTag<Real>::value, Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr,
+                                                w_trg.begin(), g_src.begin(), /*accumulate*/ 1, (int)digits, ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_transpose_host");
+  }
+
  private:
   static void RequireSupported() {
     if (!IsSupported()) {

@@ -30,7 +30,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_op_set_sources_dist", "sctl_amd_op_eval_dist", "sctl_amd_op_set_near", "sctl_amd_op_eval_potential", "sctl_amd_lists_create", "sctl_amd_lists_eval_device", "sctl_amd_lists_eval_host", "sctl_amd_lists_info", "sctl_amd_lists_destroy",
            "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host", "sctl_amd_eval_densities_device", "sctl_amd_eval_densities_host", "sctl_amd_op_eval_densities",
            "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities",
-           "sctl_amd_lists_eval_densities_device", "sctl_amd_lists_eval_densities_host", "sctl_amd_eval_lists_densities_host"]
+           "sctl_amd_lists_eval_densities_device", "sctl_amd_lists_eval_densities_host", "sctl_amd_eval_lists_densities_host",
+           "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -129,6 +130,9 @@ def lib():
     L.sctl_amd_near_apply_densities_device.argtypes = [vp, ci, vp, vp, vp]
     L.sctl_amd_op_eval_potential_densities.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, ci]
     L.sctl_amd_eval_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(i64)] * 2
+    L.sctl_amd_eval_transpose_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_transpose_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
+    L.sctl_amd_eval_transpose_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
     _LIB = L
     return L
 
@@ -221,6 +225,14 @@ def plan_densities(name, real, nd, Nt, Ns, digits=-1):
     wg, ws = C.c_int64(), C.c_int64()
     _check(lib().sctl_amd_eval_densities_plan(kernel_id(name), real, nd, Nt, Ns, digits, *[C.byref(x) for x in v], C.byref(wg), C.byref(ws)), "eval_densities_plan")
     return dict(densities_per_pass=v[0].value, passes=v[1].value, trg_per_lane=v[2].value, src_splits=v[3].value, workgroups=wg.value, workspace_bytes=ws.value)
+
+
+def plan_transpose(name, real, Nt, Ns, digits=-1):
+    """Launch plan of a transposed evaluation (sctl_amd_eval_transpose_plan): sources per lane, target splits, partial-sum workspace of one launch."""
+    t, s = C.c_int(), C.c_int()
+    ws = C.c_int64()
+    _check(lib().sctl_amd_eval_transpose_plan(kernel_id(name), real, Nt, Ns, digits, C.byref(t), C.byref(s), C.byref(ws)), "eval_transpose_plan")
+    return dict(src_per_lane=t.value, splits=s.value, workspace_bytes=ws.value)
 
 
 def counters():
@@ -359,6 +371,45 @@ def eval_device(name, r_trg, r_src, n_src, v_src, v_trg=None, digits=-1, ctx=Non
     return v_trg
 
 
+def eval_transpose_host(name, r_trg, r_src, n_src, w_trg, g_src=None, digits=-1, ctx=None, device=0, accumulate=True):
+    """The transposed sum g_src += A^T w_trg on host (numpy) arrays (sctl_amd_eval_transpose_host): w_trg holds Nt*TrgDim target weights, the
+    result Ns*SrcDim values.  A g_src of the right size is accumulated into (overwritten with accumulate=False); any other size (or None)
+    gives a fresh zeroed result, as Eval does."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    if g_src is None or g_src.size != Ns * info["k0"]:
+        g_src = np.zeros(Ns * info["k0"], dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    _check(lib().sctl_amd_eval_transpose_host(info["id"], real, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                              _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(w_trg, dt, Nt * info["k1"], "w_trg"),
+                                              _np_ptr(g_src, dt, Ns * info["k0"], "g_src"), 1 if accumulate else 0, digits, cp, cb, device), "eval_transpose_host")
+    return g_src
+
+
+def eval_transpose_device(name, r_trg, r_src, n_src, w_trg, g_src=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_transpose_device), enqueued on `stream` (default: torch's current stream); g_src of the
+    right size is accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    if g_src is None or g_src.numel() != Ns * info["k0"]:
+        g_src = torch.zeros(Ns * info["k0"], dtype=tdt, device=r_trg.device)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_transpose_device(info["id"], real, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                                    _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(w_trg, tdt, Nt * info["k1"], "w_trg"),
+                                                    _t_ptr(g_src, tdt, Ns * info["k0"], "g_src"), digits, cp, cb, C.c_void_p(st.cuda_stream)),
+               "eval_transpose_device")
+    return g_src
+
+
 def kernel_matrix_host(name, r_trg, r_src, n_src, digits=-1, ctx=None, device=0):
     """GenericKernel::KernelMatrix on numpy arrays: returns M of shape (Ns*SrcDim, Nt*TrgDim), scale included."""
     info = kernel_info(name)
@@ -446,6 +497,11 @@ class GenericKernel:
         if isinstance(r_trg, np.ndarray):
             return eval_host(self._info["id"], r_trg, r_src, n_src, v_src, v_trg, digits, self._ctx, **kw)
         return eval_device(self._info["id"], r_trg, r_src, n_src, v_src, v_trg, digits, self._ctx, **kw)
+
+    def EvalTranspose(self, g_src, r_trg, r_src, n_src, w_trg, digits=-1, **kw):
+        if isinstance(r_trg, np.ndarray):
+            return eval_transpose_host(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
+        return eval_transpose_device(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
 
     def KernelMatrix(self, M, Xt, Xs, Xn, digits=-1, **kw):
         if isinstance(Xt, np.ndarray):

@@ -105,6 +105,9 @@ namespace {
 template <class R> EvalLaunch<R> pick_eval(const KernelEntry& k, int mode, int t);
 template <> EvalLaunch<double> pick_eval<double>(const KernelEntry& k, int mode, int t) { return k.eval_f64[mode][t]; }
 template <> EvalLaunch<float> pick_eval<float>(const KernelEntry& k, int mode, int t) { return k.eval_f32[mode][t]; }
+template <class R> EvalTLaunch<R> pick_eval_t(const KernelEntry& k, int mode, int t);
+template <> EvalTLaunch<double> pick_eval_t<double>(const KernelEntry& k, int mode, int t) { return k.eval_t_f64[mode][t]; }
+template <> EvalTLaunch<float> pick_eval_t<float>(const KernelEntry& k, int mode, int t) { return k.eval_t_f32[mode][t]; }
 template <class R> MatrixLaunch<R> pick_matrix(const KernelEntry& k, int mode);
 template <> MatrixLaunch<double> pick_matrix<double>(const KernelEntry& k, int mode) { return k.matrix_f64[mode]; }
 template <> MatrixLaunch<float> pick_matrix<float>(const KernelEntry& k, int mode) { return k.matrix_f32[mode]; }
@@ -196,6 +199,63 @@ Plan make_plan(const KernelEntry& k, int real, int64_t Nt, int64_t Ns) {
   return p;
 }
 
+// The transposed evaluation (eval_transpose_kernel.hpp): make_plan with the roles exchanged — the SOURCES own the output and tile grid.x, the TARGET
+// range is split.  The partial sums [splits][owners * K0] are bounded at 2 GB by cutting the owners into several launches of owners_per_launch
+// (a multiple of a workgroup's 256 * T owners), never by taking fewer splits: the splits are what keeps a streamed chunk in one XCD's L2.
+struct PlanT {
+  int t_idx;        // index into kTTvalues
+  int splits;
+  int64_t chunk;    // targets per split (multiple of kTile)
+  int64_t owners_per_launch;
+  int64_t workspace_bytes;
+};
+constexpr int64_t kTransposeWorkspaceCap = (int64_t)2 << 30;
+// SCTL_AMD_TRANSPOSE_WORKSPACE=<bytes> lowers the bound (never raises it), read per call as SCTL_AMD_CENTERED is: a test runs the several-launch
+// cut of the owners on a small shape with it
+int64_t transpose_workspace_cap() {
+  const char* e = std::getenv("SCTL_AMD_TRANSPOSE_WORKSPACE");
+  if (!e || !e[0]) return kTransposeWorkspaceCap;
+  const long long v = std::atoll(e);
+  return (v >= 1 && v < kTransposeWorkspaceCap) ? (int64_t)v : kTransposeWorkspaceCap;
+}
+PlanT make_plan_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns) {
+  const int64_t rs = (real == SCTL_AMD_F64 ? 8 : 4);
+  const int64_t want = (int64_t)cu_count() * ((double)Nt * (double)Ns < 2147483648.0 ? 4 : 8);
+  PlanT p{};
+  const int t = (Ns >= 32768) ? 2 : 1;
+  p.t_idx = (t == 1) ? 0 : 1;
+  int64_t wg_x = (Ns + (int64_t)kBlock * t - 1) / ((int64_t)kBlock * t);
+  if (wg_x < 1) wg_x = 1;
+  const int64_t ntile = (Nt + kTile - 1) / kTile;
+  int64_t s = (want + wg_x - 1) / wg_x;
+  if (s > ntile) s = ntile;
+  if (s > 1024) s = 1024;
+  if (s < 1) s = 1;
+  if ((double)Nt * (double)Ns >= 17179869184.0) {   // one split's streamed data <= 2 MB, splits in eights, at most 64 (make_plan)
+    const int64_t trg_bytes = Nt * (3 + k.k1) * rs;
+    int64_t s2 = (trg_bytes + (2 << 20) - 1) / (2 << 20);
+    s2 = (s2 + 7) / 8 * 8;
+    if (s2 > 64) s2 = 64;
+    if (s2 > s) s = s2;
+    if (s >= 8) s = (s + 7) / 8 * 8;
+    if (s > ntile) s = ntile;
+  }
+  int64_t tiles_per = (ntile + s - 1) / s;
+  if (tiles_per < 1) tiles_per = 1;
+  p.chunk = tiles_per * kTile;
+  p.splits = (int)((Nt + p.chunk - 1) / p.chunk);
+  if (p.splits < 1) p.splits = 1;
+  p.owners_per_launch = Ns > 0 ? Ns : 1;
+  if (p.splits > 1) {
+    const int64_t group = (int64_t)kBlock * t;
+    int64_t cap = transpose_workspace_cap() / ((int64_t)p.splits * k.k0 * rs) / group * group;   // >= 2^31 / (1024 * 32 * 8) = 8192 owners
+    if (cap < group) cap = group;
+    if (p.owners_per_launch > cap) p.owners_per_launch = cap;
+  }
+  p.workspace_bytes = (p.splits > 1) ? (int64_t)p.splits * p.owners_per_launch * k.k0 * rs : 0;
+  return p;
+}
+
 int check_common(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                  int ctx_bytes, const void* ctx) {
   if (!k) return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
@@ -283,6 +343,42 @@ int eval_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const 
     hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, v, (const R*)a.partial, n,
                        p.splits, (R)(k.scale / k.acc_factor[mode]));
     HIP_TRY(hipGetLastError());
+  }
+  g_pairs += Nt * Ns;
+  g_flops += Nt * Ns * k.flops;
+  return SCTL_AMD_OK;
+}
+
+bool has_transpose(const KernelEntry& k) { return k.nrec_t > 0 && k.eval_t_f64[0][0] != nullptr; }
+int no_transpose(const KernelEntry& k) {
+  return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, std::string("kernel '") + k.name + "' has no transposed form: its functor supplies no pair_t (device/kernel_plugin.hpp)");
+}
+
+// g[s,k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] w[t,k1] on device arrays, enqueued on st
+template <class R>
+int eval_transpose_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* w, R* g, int digits,
+                            const void* ctx, hipStream_t st) {
+  if (Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  (void)hipGetLastError();
+  const PlanT p = make_plan_t(k, real, Nt, Ns);
+  const int mode = mode_for(real, digits);
+  const R scale = (R)(k.scale / k.acc_factor[mode]);
+  void* ws = nullptr;
+  if (p.splits > 1) HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+  const int64_t group = (int64_t)kBlock * kTTvalues[p.t_idx];
+  for (int64_t s0 = 0; s0 < Ns; s0 += p.owners_per_launch) {   // one launch unless the partial sums of all owners would pass 2 GB
+    const int64_t n = (Ns - s0 < p.owners_per_launch) ? Ns - s0 : p.owners_per_launch;
+    EvalTArgs<R> a{};
+    a.Nt = Nt; a.Ns = n; a.xt = xt; a.xs = xs + s0 * 3; a.xn = xn ? xn + s0 * k.nd : nullptr; a.w = w; a.g_src = g + s0 * k.k0; a.partial = (R*)ws;
+    a.chunk = p.chunk; a.scale = scale; a.ctx = make_ctx(k, ctx);
+    const dim3 grid((unsigned)((n + group - 1) / group), (unsigned)p.splits);
+    pick_eval_t<R>(k, mode, p.t_idx)(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (p.splits > 1) {
+      const int64_t m = n * k.k0;
+      hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.g_src, (const R*)a.partial, m, p.splits, scale);
+      HIP_TRY(hipGetLastError());
+    }
   }
   g_pairs += Nt * Ns;
   g_flops += Nt * Ns * k.flops;
@@ -674,6 +770,13 @@ int sctl_amd_register_kernel(const sctl_amd_kernel_desc* d) {
       return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete launch table");
     for (int t = 0; t < kNumT; t++)
       if (!e->eval_f64[m][t] || !e->eval_f32[m][t]) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete launch table");
+  }
+  {   // the transposed launchers are optional (a functor without pair_t), but all or none
+    int have = 0;
+    for (int m = 0; m < kNumMode; m++)
+      for (int t = 0; t < kNumTT; t++) have += (e->eval_t_f64[m][t] != nullptr) + (e->eval_t_f32[m][t] != nullptr);
+    if ((have != 0 && have != 2 * kNumMode * kNumTT) || (have != 0) != (e->nrec_t > 0))
+      return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete transposed launch table");
   }
   std::string why;
   const int id = registry_add(*e, &why);
@@ -1604,6 +1707,88 @@ int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64
   if (src_splits) *src_splits = s;
   if (workgroups) *workgroups = wg;
   if (workspace_bytes) *workspace_bytes = ws;
+  return SCTL_AMD_OK;
+}
+
+// ---- transposed evaluation: g_src += A^T w_trg --------------------------------------------------------------------------------------
+static int check_transpose(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                           const void* w_trg, const void* g_src, int ctx_bytes, const void* ctx) {
+  const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if ((Nt > 0 && !w_trg) || (Ns > 0 && !g_src)) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or result array");
+  if (!has_transpose(*k)) return no_transpose(*k);
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_transpose_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                   const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_transpose(k, real, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (device_count_quiet() <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (real == SCTL_AMD_F64)
+    return eval_transpose_device_t<double>(*k, real, Nt, Ns, (const double*)r_trg, (const double*)r_src, (const double*)n_src, (const double*)w_trg,
+                                           (double*)g_src, digits, ctx, (hipStream_t)stream);
+  return eval_transpose_device_t<float>(*k, real, Nt, Ns, (const float*)r_trg, (const float*)r_src, (const float*)n_src, (const float*)w_trg, (float*)g_src,
+                                        digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_transpose_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                 const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes, int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_transpose(k, real, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  const int avail = device_count_quiet();
+  if (avail <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (device < 0 || device >= avail) return fail(SCTL_AMD_ERR_NO_DEVICE, "device index out of range");
+  if (Nt == 0 || Ns == 0) return SCTL_AMD_OK;   // an empty set: nothing is read or written
+  const size_t rs = (real == SCTL_AMD_F64) ? 8 : 4;
+  DeviceScope dev_scope(device);
+  HIP_TRY(dev_scope.err);
+  HostSlot& hs = host_slot(device);   // the calling thread's slot for this device, as the forward host entry uses it
+  if (!hs.st.s) HIP_TRY(hipStreamCreateWithFlags(&hs.st.s, hipStreamNonBlocking));
+  hipStream_t st = hs.st.s;
+  struct Release { HostSlot& h; ~Release() { h.trim((size_t)64 << 20); } } release{hs};
+  const size_t b_xt = (size_t)Nt * 3 * rs, b_xs = (size_t)Ns * 3 * rs, b_xn = (size_t)Ns * k->nd * rs, b_w = (size_t)Nt * k->k1 * rs, b_g = (size_t)Ns * k->k0 * rs;
+  HIP_TRY(hs.buf[0].reserve(b_xt));
+  HIP_TRY(hs.buf[1].reserve(b_xs));
+  HIP_TRY(hs.buf[2].reserve(b_xn));
+  HIP_TRY(hs.buf[3].reserve(b_w));
+  HIP_TRY(hs.buf[4].reserve(b_g));
+  HIP_TRY(hs.stage.reserve(pad256(b_xt) + pad256(b_xs) + pad256(b_xn) + pad256(b_w) + pad256(b_g)));
+  HIP_TRY(upload(hs.buf[0].p, r_trg, b_xt, hs.stage, st));
+  HIP_TRY(upload(hs.buf[1].p, r_src, b_xs, hs.stage, st));
+  if (k->nd) HIP_TRY(upload(hs.buf[2].p, n_src, b_xn, hs.stage, st));
+  HIP_TRY(upload(hs.buf[3].p, w_trg, b_w, hs.stage, st));
+  HIP_TRY(hipMemsetAsync(hs.buf[4].p, 0, b_g, st));
+  if (real == SCTL_AMD_F64)
+    rc = eval_transpose_device_t<double>(*k, real, Nt, Ns, (const double*)hs.buf[0].p, (const double*)hs.buf[1].p, (const double*)hs.buf[2].p,
+                                         (const double*)hs.buf[3].p, (double*)hs.buf[4].p, digits, ctx, st);
+  else
+    rc = eval_transpose_device_t<float>(*k, real, Nt, Ns, (const float*)hs.buf[0].p, (const float*)hs.buf[1].p, (const float*)hs.buf[2].p,
+                                        (const float*)hs.buf[3].p, (float*)hs.buf[4].p, digits, ctx, st);
+  if (rc) return rc;
+  char* out = hs.stage.take(b_g);
+  HIP_TRY(hipMemcpyAsync(out, hs.buf[4].p, b_g, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t n = Ns * k->k0;
+  if (!accumulate) std::memcpy(g_src, out, b_g);
+  else if (real == SCTL_AMD_F64) { double* o = (double*)g_src; const double* r = (const double*)out; for (int64_t i = 0; i < n; i++) o[i] += r[i]; }
+  else { float* o = (float*)g_src; const float* r = (const float*)out; for (int64_t i = 0; i < n; i++) o[i] += r[i]; }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* src_per_lane, int* splits, int64_t* workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (!k) return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
+  if (real != SCTL_AMD_F64 && real != SCTL_AMD_F32) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "real must be SCTL_AMD_F64 or SCTL_AMD_F32");
+  if (Nt < 0 || Ns < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative size");
+  if (!has_transpose(*k)) return no_transpose(*k);
+  (void)digits;   // every accuracy mode runs the same launch geometry
+  const PlanT p = make_plan_t(*k, real, Nt, Ns);
+  if (src_per_lane) *src_per_lane = kTTvalues[p.t_idx];
+  if (splits) *splits = p.splits;
+  if (workspace_bytes) *workspace_bytes = p.workspace_bytes;
   return SCTL_AMD_OK;
 }
 
