@@ -233,6 +233,33 @@ int sctl_amd_eval_transpose_host(int kernel, int real, int64_t Nt, int64_t Ns, c
  * of one launch.  Those stay within 2 GB: the sources are cut into several launches rather than the targets into fewer splits. */
 int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* src_per_lane, int* splits, int64_t* workspace_bytes);
 
+/* ---- gradients of <w_trg, A v_src> with respect to the geometry ------------------------------------------------------------------ */
+/* With L = sum_t sum_k1 w_trg[t*TrgDim + k1] * v_trg[t*TrgDim + k1], v_trg = A v_src as sctl_amd_eval_* computes it, d = x_t - x_s and the pair's scalar
+ *     phi_ts = sum_k0 sum_k1 w_trg[t*TrgDim + k1] * U(d, n_s)[k0][k1] * v_src[s*SrcDim + k0],
+ * these entries add the derivatives of L with respect to the coordinates of both point sets and to the source normals:
+ *     g_trg[t*3 + j] +=  scale * sum_s d phi_ts / d d_j        (Nt x 3)
+ *     g_src[s*3 + j] += -scale * sum_t d phi_ts / d d_j        (Ns x 3)
+ *     g_nrm[s*3 + j] +=  scale * sum_t d phi_ts / d n_j        (Ns x NormalDim; kernels with a normal only)
+ * — forces of a pair potential, shape derivatives of a boundary, the geometry half of a differentiable kernel sum (the density half is
+ * sctl_amd_eval_transpose_*).  Any of the three outputs may be null and is then not computed; g_trg comes from a pass whose lanes own targets, g_src and
+ * g_nrm together from one whose lanes own sources, and a pass none of whose outputs is asked for is not launched.  g_nrm non-null for a kernel without a
+ * normal is SCTL_AMD_ERR_BAD_ARGUMENT.  A coincident pair contributes 0 to all three; Helmholtz: v_src, w_trg are (re, im) pairs, L is the real sum over
+ * both components, and k is not differentiated.  `digits`, `ctx` and the argument checks are those of the forward and transposed entries; a registered
+ * kernel whose functor has no gradient form (no pair_g: device/kernel_plugin.hpp) is SCTL_AMD_ERR_UNKNOWN_KERNEL here only.  The exact all-pairs scheme
+ * on one device (device/eval_grad_kernel.hpp): sums in a fixed order, no atomics, bit-reproducible.  Counters grow by Nt*Ns pairs per pass launched.
+ * Nt == 0 or Ns == 0: nothing is read or written. */
+/* DEVICE arrays; enqueued on `stream`; the outputs are accumulated into. */
+int sctl_amd_eval_grad_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                              const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes, void* stream);
+/* HOST arrays, one device; returns when the outputs are final.  accumulate != 0 adds to them, 0 overwrites them. */
+int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                            const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int accumulate, int digits, const void* ctx, int ctx_bytes, int device);
+/* The plan of such a call (no side effects, no GPU needed), per pass: owners per lane, splits of the streamed range, and the bytes of partial sums of
+ * one launch (3 sums per target; 3, or 6 with a normal, per source).  Those stay within 2 GB: the owners are cut into several launches rather than the
+ * streamed set into fewer splits. */
+int sctl_amd_eval_grad_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* trg_per_lane, int* trg_splits, int64_t* trg_workspace_bytes,
+                            int* src_per_lane, int* src_splits, int64_t* src_workspace_bytes);
+
 /* ---- rank-parallel evaluation: one process per GPU (ParticleFMM::EvalDirect under MPI, fmm-wrapper.txx:504-561) --------------- */
 /* The reference partitions targets and sources over MPI ranks and rotates the source blocks round a ring (:537-558).  Here every
  * rank keeps ITS targets, and the sources (and, per evaluation, the densities) of ALL ranks are all-gathered into each rank's

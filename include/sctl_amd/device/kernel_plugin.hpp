@@ -42,6 +42,15 @@
 // registers; unused R[1] when ND == 0), the same masking rule, accuracy modes and acc_factor(mode) as pair().  `finish_t<R>(R (&acc)[K0])` /
 // `finish_t_mode<R, MODE>` are the optional counterparts of finish / finish_mode.  Without pair_t the kernel registers and runs as before and
 // the transposed entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for it (tests/plugin/yukawa_kernel.hip has none, yukawa_t_kernel.hip has one).
+// Optional, the GRADIENT form (sctl_amd_eval_grad_*: the derivatives of <w, A f> with respect to the coordinates of both point sets and the source normals).  A functor
+// that supplies
+//     template <class R, int MODE, bool MASKED, bool WANT_N>
+//     static __device__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1],
+//                                   const sctl_amd::KerCtx& ctx, const Consts<R>& K);
+// gets them: with phi = sum_k0 sum_k1 w[k1] U(d, n)[k0][k1] f[k0] it adds d phi / d d_j to G[j] and, where WANT_N, d phi / d n_j to N[j]; the same d, masking
+// rule and accuracy modes as pair(), plain f and w (no record).  It is called from both sides of the evaluator (targets own the sums / sources own them).  The sums
+// are taken as the derivative itself unless `static constexpr double grad_factor(int mode)` names the multiple pair_g accumulates.  Without pair_g the gradient
+// entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for the kernel and everything else runs as before.
 // A kernel with per-launch constants of its own supplies a Consts type instead of DefaultConsts: it is built once per workgroup from
 // (double* lds) or, when it has such a constructor, from (double* lds, const KerCtx& ctx) — e.g. to derive scalar-register constants
 // from a wavenumber (ukernels.hpp: HelmholtzConsts) — and handed to every pair() call.

@@ -3,6 +3,7 @@
 #pragma once
 #include "eval_kernel.hpp"
 #include "eval_transpose_kernel.hpp"
+#include "eval_grad_kernel.hpp"
 #include "lists_kernel.hpp"
 
 namespace sctl_amd {
@@ -15,6 +16,7 @@ constexpr int kTTvalues[kNumTT] = {1, 2};
 
 template <class R> using EvalLaunch = void (*)(const EvalArgs<R>&, dim3 grid, hipStream_t);
 template <class R> using EvalTLaunch = void (*)(const EvalTArgs<R>&, dim3 grid, hipStream_t);
+template <class R> using EvalGLaunch = void (*)(const EvalGArgs<R>&, dim3 grid, hipStream_t);
 template <class R> using MatrixBatchLaunch = void (*)(const MatTile* tiles, int64_t ntiles, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, hipStream_t);
 template <class R> using ListsLaunch = void (*)(const ListArgs<R>&, int64_t nblocks, hipStream_t);
 template <class R> using MatrixLaunch = void (*)(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, dim3 grid, hipStream_t);
@@ -36,13 +38,26 @@ struct KernelEntry {
   int nrec_t;
   EvalTLaunch<double> eval_t_f64[kNumMode][kNumTT];
   EvalTLaunch<float> eval_t_f32[kNumMode][kNumTT];  // modes 0 and 1 only (mode 2 aliases mode 1)
+  // the gradient evaluator (eval_grad_kernel.hpp), side 0 target-owned, side 1 source-owned: all null, and grad_t 0, for a functor without pair_g
+  int grad_t[2];                                    // owners per lane of each side (GradOwnersOf)
+  double grad_factor[kNumMode];                     // pair_g() of mode m accumulates grad_factor[m] x the derivative (GradFactorOf)
+  EvalGLaunch<double> eval_g_f64[kNumMode][2];
+  EvalGLaunch<float> eval_g_f32[kNumMode][2];       // modes 0 and 1 only (mode 2 aliases mode 1)
 };
+
+// Owners per lane of the gradient evaluator, per kernel and side.  One everywhere: a gradient pair is two to four times the forward pair's arithmetic, so
+// the LDS reads a second owner would share are a small part of it, and every form then keeps ScratchSize 0 and at least two waves per SIMD with room
+// to spare (two owners per lane have not been timed).
+template <class Ker, int SIDE> struct GradOwnersOf { static constexpr int value = 1; };
 
 template <class Ker, class R, int MODE, int T> void launch_eval(const EvalArgs<R>& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL((eval_kernel<Ker, R, MODE, T>), grid, dim3(kBlock), 0, st, a);
 }
 template <class Ker, class R, int MODE, int T> void launch_eval_t(const EvalTArgs<R>& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL((eval_transpose_kernel<Ker, R, MODE, T>), grid, dim3(kBlock), 0, st, a);
+}
+template <class Ker, class R, int MODE, int SIDE> void launch_eval_g(const EvalGArgs<R>& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((eval_grad_kernel<Ker, R, MODE, SIDE, GradOwnersOf<Ker, SIDE>::value>), grid, dim3(kBlock), 0, st, a);
 }
 template <class Ker, class R, int MODE> void launch_matrix(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, R* M, R scale,
                                                            const KerCtx& ctx, dim3 grid, hipStream_t st) {
@@ -83,6 +98,14 @@ template <class Ker> KernelEntry make_entry(int ctx_bytes) {
     SCTL_AMD_ROW_T(float, e.eval_t_f32, 0, 0) SCTL_AMD_ROW_T(float, e.eval_t_f32, 1, 1) SCTL_AMD_ROW_T(float, e.eval_t_f32, 2, 1)
 #undef SCTL_AMD_ROW_T
   }
+  if constexpr (HasPairG<Ker>::value) {
+    e.grad_t[0] = GradOwnersOf<Ker, 0>::value; e.grad_t[1] = GradOwnersOf<Ker, 1>::value;
+    for (int m = 0; m < kNumMode; m++) e.grad_factor[m] = GradFactorOf<Ker>::value(m);
+#define SCTL_AMD_ROW_G(R, arr, M, MM) arr[M][0] = launch_eval_g<Ker, R, MM, 0>; arr[M][1] = launch_eval_g<Ker, R, MM, 1>;
+    SCTL_AMD_ROW_G(double, e.eval_g_f64, 0, 0) SCTL_AMD_ROW_G(double, e.eval_g_f64, 1, 1) SCTL_AMD_ROW_G(double, e.eval_g_f64, 2, 2)
+    SCTL_AMD_ROW_G(float, e.eval_g_f32, 0, 0) SCTL_AMD_ROW_G(float, e.eval_g_f32, 1, 1) SCTL_AMD_ROW_G(float, e.eval_g_f32, 2, 1)
+#undef SCTL_AMD_ROW_G
+  }
   return e;
 }
 
@@ -109,6 +132,29 @@ SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FSxU)
 SCTL_AMD_EVAL_T_INSTANCES(extern, Stokes3D_FxUP)
 SCTL_AMD_EVAL_T_INSTANCES(extern, Laplace3D_FDxUdU)
 SCTL_AMD_EVAL_T_INSTANCES(extern, Helmholtz3D_FxU)
+
+// ... and the gradient launchers in inst_g_*.hip
+#define SCTL_AMD_EVAL_G_INSTANCES(PREFIX, Ker)                                                              \
+  PREFIX template void launch_eval_g<Ker, double, 0, 0>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, double, 0, 1>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, double, 1, 0>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, double, 1, 1>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, double, 2, 0>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, double, 2, 1>(const EvalGArgs<double>&, dim3, hipStream_t);       \
+  PREFIX template void launch_eval_g<Ker, float, 0, 0>(const EvalGArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_g<Ker, float, 0, 1>(const EvalGArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_g<Ker, float, 1, 0>(const EvalGArgs<float>&, dim3, hipStream_t);         \
+  PREFIX template void launch_eval_g<Ker, float, 1, 1>(const EvalGArgs<float>&, dim3, hipStream_t);
+SCTL_AMD_EVAL_G_INSTANCES(extern, Laplace3D_FxU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Laplace3D_DxU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Laplace3D_FxdU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FxU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_DxU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FxT)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FSxU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FxUP)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Laplace3D_FDxUdU)
+SCTL_AMD_EVAL_G_INSTANCES(extern, Helmholtz3D_FxU)
 
 // defined in inst_*.hip
 const KernelEntry& entry_Laplace3D_FxU();

@@ -27,6 +27,14 @@
 //   pair_t<R,MODE,MASKED[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[k0] += sum_k1 U(d, n)[k0][k1] w[k1] with the SAME d = x_trg - x_src as pair(), n the owner's
 //                              normal (R[3], or R[1] unused when ND == 0) from registers.  Same rsqrt helpers, modes, masking and acc_factor as pair().
 //   finish_t<R>(acc) / finish_t_mode<R,MODE>(acc)   optional, applied once to a source's K0 sums (FinishTOf)
+// and the gradient form used by eval_grad_kernel.hpp from both of its sides (the pair's scalar phi = sum_k0 sum_k1 w[k1] U(d, n)[k0][k1] f[k0]):
+//   pair_g<R,MODE,MASKED[,VARIANT],WANT_N>(G, N, d, n, f, w, ctx, K)   G[j] += d phi / d d_j and, where WANT_N, N[j] += d phi / d n_j, with the SAME
+//                              d = x_trg - x_src as pair(); n (R[3], or R[1] unused when ND == 0), f[K0] and w[K1] are the plain inputs, from registers
+//                              on the owner's side and from the streamed record on the other.  Every phi is a sum of terms P(d, n, f, w) r^-p with P
+//                              polynomial, so grad phi = sum (grad P y^p - p P y^(p+2) d) with y = 1/r: the forms below take the NORMALISED
+//                              rsqrt_masked<MODE, MASKED> (rsqrt_grad: fp32 always refined) (a gradient mixes the powers p and p + 2, and its owner holds no record a factor could be
+//                              folded into), so the sums need no per-mode factor.  A kernel that accumulates a multiple anyway names it in the
+//                              optional grad_factor(mode) (GradFactorOf; Helmholtz3D_FxU: its tables reduce the mode's C r).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -229,6 +237,15 @@ template <class Ker, class R, int MODE> struct FinishTOf<Ker, R, MODE, void, std
 };
 template <class Ker, class R, int MODE> __device__ __forceinline__ void finish_t_acc(R (&acc)[Ker::K0]) { FinishTOf<Ker, R, MODE>::apply(acc); }
 
+// The gradient form of a kernel (pair_g) is optional too: a functor without it evaluates A and, with pair_t, A^T only.  HasPairG detects it in either
+// spelling, pair_g<R, MODE, MASKED, WANT_N> or, for a kernel with launch-uniform variants, pair_g<R, MODE, MASKED, VARIANT, WANT_N>.
+template <class Ker, class = void, class = void> struct HasPairG : std::false_type {};
+template <class Ker, class V> struct HasPairG<Ker, std::void_t<decltype(&Ker::template pair_g<double, 0, true, false>)>, V> : std::true_type {};
+template <class Ker> struct HasPairG<Ker, void, std::void_t<decltype(&Ker::template pair_g<double, 0, true, 0, false>)>> : std::true_type {};
+// pair_g of mode m accumulates GradFactorOf<Ker>::value(m) x the derivative: Ker::grad_factor(m) when named, else 1
+template <class Ker, class = void> struct GradFactorOf { static constexpr double value(int) { return 1; } };
+template <class Ker> struct GradFactorOf<Ker, std::void_t<decltype(Ker::grad_factor(0))>> { static constexpr double value(int mode) { return Ker::grad_factor(mode); } };
+
 // Per-kernel constants of a launch: Consts(lds, capacity, ctx) when the type takes the scratch capacity (in doubles) and the context,
 // Consts(lds, ctx) when it takes the context, Consts(lds) otherwise.
 template <class KC> __device__ __forceinline__ KC make_consts(double* lds, int lds_doubles, const KerCtx& ctx) {
@@ -361,6 +378,21 @@ template <int MODE, int P, bool MASKED, class R> __device__ __forceinline__ R rs
 // (exact) for the Newton step, A^2 (A has 24 bits: exact) for the cubic step, 1 for the bare seed.
 constexpr double rsqrt_scaled_c2(int mode) { return rsqrt_scaled_factor(mode, 1) == 1 ? 1.0 : mode == 1 ? 4.0 : cubic83_factor(1) * cubic83_factor(1); }
 
+// 1/r of the gradient forms: the normalised rsqrt_masked of the mode, except that fp32 never takes the bare seed.  A gradient raises y to the powers p + 2 = 3 .. 7,
+// so the seed's 2^-23.3 becomes several ulp per pair, and it does not average out over a sum (measured, Laplace3D-FDxUdU fp32 300 x 2000: rel-L2 5.1e-7 with the seed,
+// 2.0e-7 with one Newton step, 0.7e-7 for the same formula in torch float32): "full precision of fp32" costs the gradient three more fp32 instructions per pair.
+template <int MODE, bool MASKED, class R> __device__ __forceinline__ R rsqrt_grad(R r2, const RsqConst<R>& K) {
+  return rsqrt_masked<(std::is_same<R, float>::value && MODE == 0) ? 1 : MODE, MASKED>(r2, K);
+}
+
+// The gradient of the Stokeslet family, phi = fw y + A B y^3 with y = 1/r, A and B linear in d with gradients f and w (three components each):
+//   grad phi = y^3 (B f + A w - d (fw + 3 A B y^2))
+template <class R> __device__ __forceinline__ void stokeslet_grad(R (&G)[3], const R (&d)[3], R y, const R* f, const R* w, R A, R B, R fw) {
+  const R y2 = y * y, y3 = y2 * y;
+  const R c = fma_((A * B) * R(3), y2, fw);
+#pragma unroll
+  for (int j = 0; j < 3; j++) G[j] = fma_(y3, fma_(B, f[j], fma_(A, w[j], -(c * d[j]))), G[j]);
+}
 
 // ---- multi-density records (pack_m / pair_m of every struct below) -------------------------------------------------
 constexpr int nrec_multi(int nd, int k0, int m) { return (3 + nd + m * k0 + 1) / 2 * 2; }
@@ -406,6 +438,13 @@ struct Laplace3D_FxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(rec[3], rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq), acc[0]);
   }
+  // gradient: phi = w f y, grad_d = -(w f) y^3 d
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R t = (f[0] * w[0]) * ((y * y) * y);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(-t, d[j], G[j]);
+  }
 };
 
 // ---- Laplace double layer: u = (r.n) f / r^3   (kernel_functions.hpp:33-51); record holds n*f ------------
@@ -434,6 +473,19 @@ struct Laplace3D_DxU {
   template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) { rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; }
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(dot3(d, n), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq) * rec[3], acc[0]);
+  }
+  // gradient: phi = c (d.n) y^3 with c = w f: grad_d = c y^3 (n - 3 (d.n) y^2 d), grad_n = c y^3 d
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R a = (f[0] * w[0]) * (y2 * y);
+    const R b = (dot3(d, n) * R(-3)) * (y2 * a);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(a, n[j], fma_(b, d[j], G[j]));
+    if constexpr (WANT_N) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(a, d[j], N[j]);
+    }
   }
 };
 
@@ -468,6 +520,15 @@ struct Laplace3D_FxdU {
   }
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(dot3(d, rec + 3), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq), acc[0]);
+  }
+  // gradient: phi = f (d.w) y^3: grad_d = f y^3 (w - 3 (d.w) y^2 d), the double layer's with w for n
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R a = f[0] * (y2 * y);
+    const R b = (dot3(d, w) * R(-3)) * (y2 * a);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(a, w[j], fma_(b, d[j], G[j]));
   }
 };
 
@@ -510,6 +571,11 @@ struct Stokes3D_FxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     pair<R, MODE, MASKED>(acc, d, rec, KerCtx{}, K);
   }
+  // gradient: phi = (f.w) y + (d.f)(d.w) y^3 (stokeslet_grad)
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    stokeslet_grad(G, d, y, f, w, dot3(d, f), dot3(d, w), dot3(f, w));
+  }
 };
 
 // ---- stresslet: u_j = r_j (r.f)(r.n) / r^5, scale 3/(4 pi)   (kernel_functions.hpp:97-120) ----------------
@@ -547,6 +613,22 @@ struct Stokes3D_DxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     const R t = dot3(d, n) * dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
+  }
+  // gradient: phi = a b c y^5 with a = d.n, b = d.f, c = d.w: grad_d = y^5 (bc n + ac f + ab w - 5 abc y^2 d), grad_n = bc y^5 d
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    const R a = dot3(d, n), b = dot3(d, f), c = dot3(d, w);
+    const R bc = b * c, ac = a * c, ab = a * b;
+    const R e = (ab * c) * (y2 * R(-5));
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(bc, n[j], fma_(ac, f[j], fma_(ab, w[j], e * d[j]))), G[j]);
+    if constexpr (WANT_N) {
+      const R t = bc * y5;
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(t, d[j], N[j]);
+    }
   }
 };
 
@@ -605,6 +687,21 @@ struct Stokes3D_FxT {
     const R t = q * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
   }
+  // gradient: phi = A q y^5 with A = d.f and q = d^T W d, W = w[j*3+k]: with v = (W + W^T) d = grad q and q = (d.v) / 2,
+  //   grad_d = y^5 (q f + A v - 5 A q y^2 d)
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    R v[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) v[j] = fma_(w[j * 3 + 2] + w[6 + j], d[2], fma_(w[j * 3 + 1] + w[3 + j], d[1], (w[j * 3] + w[j]) * d[0]));
+    const R q = dot3(d, v) * R(0.5);
+    const R A = dot3(d, f);
+    const R e = (A * q) * (y2 * R(-5));
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(q, f[j], fma_(A, v[j], e * d[j])), G[j]);
+  }
 };
 
 // ---- Stokeslet + source/sink: u_j = f_j / r + ((r.f) + f_3) r_j / r^3   (kernel_functions.hpp:148-172) ------
@@ -651,6 +748,11 @@ struct Stokes3D_FSxU {
     const R t = dot3(d, rec + 3) * (y * y);
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[6 + j]), acc[j]);
     acc[3] = fma_(t, y, acc[3]);
+  }
+  // gradient: phi = (f.w) y + ((d.f) + f_3)(d.w) y^3, the Stokeslet's with A = (d.f) + f_3 (stokeslet_grad)
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    stokeslet_grad(G, d, y, f, w, fma_(d[2], f[2], fma_(d[1], f[1], fma_(d[0], f[0], f[3]))), dot3(d, w), dot3(w, f));
   }
 };
 
@@ -699,6 +801,11 @@ struct Stokes3D_FxUP {
     const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
     const R t = fma_(d[2], rec[5], fma_(d[1], rec[4], fma_(d[0], rec[3], rec[6]))) * (y * y);
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[7 + j]), acc[j]);
+  }
+  // gradient: phi = (f.w_u) y + (d.f)((d.w_u) + w_p) y^3, the Stokeslet's with B = (d.w_u) + w_p (stokeslet_grad)
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    stokeslet_grad(G, d, y, f, w, dot3(d, f), fma_(d[2], w[2], fma_(d[1], w[1], fma_(d[0], w[0], w[3]))), dot3(f, w));
   }
 };
 
@@ -780,6 +887,31 @@ struct Laplace3D_FDxUdU {
     const R e = fma_(-a, K.c3, rec[3]);                     // C^2 (w_u - 3 (d.w_g) / r^2)
     const R h = fma_(n[2], rec[9], fma_(n[1], rec[8], fma_(n[0], rec[7], dot3(d, n) * e)));
     acc[1] = fma_(y3, h, acc[1]);
+  }
+  // gradient: with q = f[0], mu = f[1], w_u = w[0], w_g = w[1..3], dn = d.n, B = d.w_g, nw = n.w_g the pair's scalar is
+  //   phi = a1 y + P3 y^3 + P5 y^5,    a1 = w_u q,    P3 = mu (w_u dn + nw) - q B,    P5 = -3 mu dn B
+  //   grad_d = -y^3 (a1 + y^2 (3 P3 + 5 P5 y^2)) d + y^3 (w_u mu n - q w_g) - 3 mu y^5 (B n + dn w_g)
+  //   grad_n = mu y^3 (w_u d + w_g) - 3 mu B y^5 d
+  template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y3 = y2 * y;
+    const R q = f[0], mu = f[1], wu = w[0];
+    const R* wg = w + 1;
+    const R dn = dot3(d, n), B = dot3(d, wg), nw = dot3(n, wg);
+    const R h0 = -(y2 * K.c3);                               // -3 y^2: the y^5 terms inside the y^3 bracket
+    const R h = mu * h0;
+    const R P3 = fma_(mu, fma_(wu, dn, nw), -(q * B));
+    const R P5 = (mu * K.c3) * (-dn * B);
+    const R cd = -y3 * fma_(y2, fma_(P5 * R(5), y2, P3 * K.c3), wu * q);
+    const R cn = fma_(h, B, wu * mu), cw = fma_(h, dn, -q);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(cd, d[j], fma_(y3, fma_(cn, n[j], cw * wg[j]), G[j]));
+    if constexpr (WANT_N) {
+      const R mu3 = mu * y3, e = fma_(h0, B, wu);
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(mu3, fma_(e, d[j], wg[j]), N[j]);
+    }
   }
   template <class R, int MODE> static __device__ __forceinline__ void finish_t_mode(R (&acc)[K0]) { acc[0] *= R(rsqrt_scaled_c2(MODE)); }
 };
@@ -869,6 +1001,34 @@ struct Helmholtz3D_FxU {
     }
     acc[0] = fma_(gr, rec[3], fma_(gi, rec[4], acc[0]));
     acc[1] = fma_(gr, rec[4], fma_(-gi, rec[3], acc[1]));
+  }
+  // gradient: with c = conj(w) f and G = e^{ikr} / r the pair's scalar is phi = Re(c G), and dG/dr = (ik - 1/r) G, so
+  //   grad_d = Re((ik - y) c G) y d,    Re((ik - y) H) = -(Im k + y) H_re - (Re k) H_im,    y = 1/r
+  // G comes from the same tables and variants as pair(), i.e. as C G on the mode's unnormalised C / r: grad_factor carries the C, and y = (C / r) / C.
+  static constexpr double grad_factor(int mode) { return rsqrt_scaled_factor(mode, 1); }
+  template <class R, int MODE, bool MASKED, int VARIANT, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&)[1], const R (&d)[3], const R (&)[1], const R (&f)[K0], const R (&w)[K1], const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+    const R y = rinv * R(K.cinv);
+    const R cr = fma_(w[1], f[1], w[0] * f[0]), ci = fma_(-w[1], f[0], w[0] * f[1]);
+    const R hr = fma_(-ci, gi, cr * gr), hi = fma_(ci, gr, cr * gi);
+    const R a = REAL_K ? y : y + R(ctx.v[1]);
+    const R t = -fma_(R(ctx.v[0]), hi, a * hr) * y;
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(t, d[j], G[j]);
   }
   // fp64, one reduction of r for the whole factor e^{ikr} (fastmath.hpp: cexp_tab_k); returns G = e^{ikr} / r.  The speculative pass runs it
   // unconditionally and records the largest distance; the careful pass branches per pair to libm beyond the table's range.

@@ -206,6 +206,37 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_transpose_host");
   }
 
+  // The gradients of L = <w_trg, A v_src> with respect to the geometry (sctl_amd_eval_grad_host; not in the reference): with d = x_t - x_s and
+  // phi_ts = sum_k0 sum_k1 w_trg[t*TrgDim + k1] U(d, n_s)[k0][k1] v_src[s*SrcDim + k0],
+  //   g_trg[t*DIM + j] += scale sum_s d phi_ts / d d_j,    g_src[s*DIM + j] -= scale sum_t d phi_ts / d d_j,    g_nrm[s*DIM + j] += scale sum_t d phi_ts / d n_j.
+  // A null output is not computed; g_nrm must be null for a kernel without a normal.  Each output follows Eval's rule: the right size is accumulated
+  // into, any other is resized and zeroed.
+  template <class Real, Integer digits = -1>
+  void EvalGrad(Vector<Real>* g_trg, Vector<Real>* g_src, Vector<Real>* g_nrm, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src,
+                const Vector<Real>& v_src, const Vector<Real>& w_trg) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM;
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(v_src.Dim() == Ns * KDIM0);
+    SCTL_AMD_ASSERT(w_trg.Dim() == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(!g_nrm || N_DIM);
+    auto size = [](Vector<Real>* g, Long n) {
+      if (g && g->Dim() != n) {
+        g->ReInit(n);
+        g->SetZero();
+      }
+    };
+    size(g_trg, Nt * DIM);
+    size(g_src, Ns * DIM);
+    size(g_nrm, Ns * DIM);
+    RequireSupported();
+    const int rc = sctl_amd_eval_grad_host(DeviceKernelId(), RealTag<Real>::value, Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, v_src.begin(),
+                                           w_trg.begin(), g_trg ? g_trg->begin() : nullptr, g_src ? g_src->begin() : nullptr, g_nrm ? g_nrm->begin() : nullptr,
+                                           /*accumulate*/ 1, (int)digits, ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_grad_host");
+  }
+
  private:
   static void RequireSupported() {
     if (!IsSupported()) {

@@ -31,7 +31,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_lists_device", "sctl_amd_eval_lists_host", "sctl_amd_eval_densities_device", "sctl_amd_eval_densities_host", "sctl_amd_op_eval_densities",
            "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities",
            "sctl_amd_lists_eval_densities_device", "sctl_amd_lists_eval_densities_host", "sctl_amd_eval_lists_densities_host",
-           "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan"]
+           "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan",
+           "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -133,6 +134,9 @@ def lib():
     L.sctl_amd_eval_transpose_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_transpose_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
+    L.sctl_amd_eval_grad_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_grad_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
+    L.sctl_amd_eval_grad_plan.argtypes = [ci, ci, i64, i64, ci] + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)] * 2
     _LIB = L
     return L
 
@@ -233,6 +237,15 @@ def plan_transpose(name, real, Nt, Ns, digits=-1):
     ws = C.c_int64()
     _check(lib().sctl_amd_eval_transpose_plan(kernel_id(name), real, Nt, Ns, digits, C.byref(t), C.byref(s), C.byref(ws)), "eval_transpose_plan")
     return dict(src_per_lane=t.value, splits=s.value, workspace_bytes=ws.value)
+
+
+def plan_grad(name, real, Nt, Ns, digits=-1):
+    """Launch plan of a gradient evaluation (sctl_amd_eval_grad_plan), per pass ("trg": the targets own the sums, "src": the sources do): owners per
+    lane, splits of the streamed range, partial-sum workspace of one launch."""
+    v = [C.c_int(), C.c_int(), C.c_int64(), C.c_int(), C.c_int(), C.c_int64()]
+    _check(lib().sctl_amd_eval_grad_plan(kernel_id(name), real, Nt, Ns, digits, *[C.byref(x) for x in v]), "eval_grad_plan")
+    return dict(trg=dict(per_lane=v[0].value, splits=v[1].value, workspace_bytes=v[2].value),
+                src=dict(per_lane=v[3].value, splits=v[4].value, workspace_bytes=v[5].value))
 
 
 def counters():
@@ -410,6 +423,60 @@ def eval_transpose_device(name, r_trg, r_src, n_src, w_trg, g_src=None, digits=-
     return g_src
 
 
+def _grad_wanted(info, want):
+    if want is None:
+        want = ("trg", "src", "nrm") if info["nd"] else ("trg", "src")
+    bad = [x for x in want if x not in ("trg", "src", "nrm")]
+    if bad:
+        raise SctlAmdError("want holds 'trg', 'src' and 'nrm' only, not %r" % (bad,))
+    return tuple(x in want for x in ("trg", "src", "nrm"))
+
+
+def eval_grad_host(name, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1, ctx=None, device=0, accumulate=True):
+    """Gradients of L = <w_trg, A v_src> with respect to the target coordinates, the source coordinates and the source normals on host (numpy)
+    arrays (sctl_amd_eval_grad_host).  `want` names the outputs to compute, of "trg", "src", "nrm" (default: all the kernel has); returns
+    (g_trg, g_src, g_nrm), each Nt*3 or Ns*3 values, None where not wanted.  An output array of the right size is accumulated into (overwritten
+    with accumulate=False); any other size (or None) gives a fresh zeroed result, as Eval does."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    out = []
+    for wanted, g, n in zip(_grad_wanted(info, want), (g_trg, g_src, g_nrm), (Nt * 3, Ns * 3, Ns * 3)):
+        out.append(None if not wanted else g if g is not None and g.size == n else np.zeros(n, dtype=dt))
+    keep, cp, cb = _ctx_blob(info, ctx)
+    ptr = [None if g is None else _np_ptr(g, dt, g.size, what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+    _check(lib().sctl_amd_eval_grad_host(info["id"], real, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                         _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(v_src, dt, Ns * info["k0"], "v_src"),
+                                         _np_ptr(w_trg, dt, Nt * info["k1"], "w_trg"), ptr[0], ptr[1], ptr[2], 1 if accumulate else 0, digits, cp, cb, device),
+           "eval_grad_host")
+    return tuple(out)
+
+
+def eval_grad_device(name, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_grad_device), enqueued on `stream` (default: torch's current stream); outputs of the right
+    size are accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    out = []
+    for wanted, g, n in zip(_grad_wanted(info, want), (g_trg, g_src, g_nrm), (Nt * 3, Ns * 3, Ns * 3)):
+        out.append(None if not wanted else g if g is not None and g.numel() == n else torch.zeros(n, dtype=tdt, device=r_trg.device))
+    keep, cp, cb = _ctx_blob(info, ctx)
+    ptr = [None if g is None else _t_ptr(g, tdt, g.numel(), what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_grad_device(info["id"], real, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                               _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(v_src, tdt, Ns * info["k0"], "v_src"),
+                                               _t_ptr(w_trg, tdt, Nt * info["k1"], "w_trg"), ptr[0], ptr[1], ptr[2], digits, cp, cb,
+                                               C.c_void_p(st.cuda_stream)), "eval_grad_device")
+    return tuple(out)
+
+
 def kernel_matrix_host(name, r_trg, r_src, n_src, digits=-1, ctx=None, device=0):
     """GenericKernel::KernelMatrix on numpy arrays: returns M of shape (Ns*SrcDim, Nt*TrgDim), scale included."""
     info = kernel_info(name)
@@ -502,6 +569,11 @@ class GenericKernel:
         if isinstance(r_trg, np.ndarray):
             return eval_transpose_host(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
         return eval_transpose_device(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
+
+    def EvalGrad(self, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
+        if isinstance(r_trg, np.ndarray):
+            return eval_grad_host(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
+        return eval_grad_device(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
 
     def KernelMatrix(self, M, Xt, Xs, Xn, digits=-1, **kw):
         if isinstance(Xt, np.ndarray):

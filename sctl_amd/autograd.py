@@ -4,8 +4,12 @@ is the transposed sum A^T (dloss/du) — sctl_amd_eval_transpose_device, on the 
     u = sctl_amd.autograd.kernel_sum("Stokes3D-FxUP", r_trg, r_src, None, v_src)      # torch CUDA tensors; v_src.requires_grad
     u.square().sum().backward()                                                      # v_src.grad = A^T (2 u)
 
-Only the densities are differentiated: gradients with respect to the coordinates or the normals need the kernels' derivatives, which this
-library does not have, so a coordinate or normal tensor that requires grad is refused instead of silently getting none."""
+kernel_sum differentiates the densities only, and refuses a coordinate or normal tensor that requires grad instead of silently giving it none.
+kernel_sum_geometry differentiates the geometry as well: its backward adds sctl_amd_eval_grad_device, the kernels' derivatives (pair_g), for whichever
+of r_trg, r_src, n_src need a gradient.
+
+    u = sctl_amd.autograd.kernel_sum_geometry("Laplace3D-DxU", r_trg, r_src, n_src, v_src)   # any of the four may require grad
+    u.square().sum().backward()                                                               # r_trg.grad, r_src.grad, n_src.grad, v_src.grad"""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -34,6 +38,40 @@ def kernel_sum(name, r_trg, r_src, n_src, v_src, digits=-1, ctx=None):
     """GenericKernel::Eval on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to v_src."""
     for what, t in (("r_trg", r_trg), ("r_src", r_src), ("n_src", n_src)):
         if t is not None and t.requires_grad:
-            raise api.SctlAmdError("kernel_sum differentiates with respect to the densities only: %s requires grad, and gradients with respect to "
-                                   "coordinates or normals are not implemented" % what)
+            raise api.SctlAmdError("kernel_sum differentiates with respect to the densities only: %s requires grad; kernel_sum_geometry differentiates "
+                                   "coordinates and normals too" % what)
     return _KernelSum.apply(name, r_trg, r_src, n_src, v_src, digits, ctx)
+
+
+class _KernelSumGeometry(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, name, r_trg, r_src, n_src, v_src, digits, ctx):
+        fn_ctx.kernel = (name, digits, ctx)
+        r_trg, r_src, v_src = r_trg.detach().contiguous(), r_src.detach().contiguous(), v_src.detach().contiguous()
+        n_src = None if n_src is None else n_src.detach().contiguous()
+        fn_ctx.has_normal = n_src is not None
+        fn_ctx.shapes = (r_trg.shape, r_src.shape, None if n_src is None else n_src.shape)
+        fn_ctx.save_for_backward(*([r_trg, r_src, v_src] + ([n_src] if n_src is not None else [])))
+        return api.eval_device(name, r_trg, r_src, n_src, v_src, digits=digits, ctx=ctx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_u):
+        name, digits, ctx = fn_ctx.kernel
+        r_trg, r_src, v_src = fn_ctx.saved_tensors[:3]
+        n_src = fn_ctx.saved_tensors[3] if fn_ctx.has_normal else None
+        grad_u = grad_u.contiguous()
+        need = fn_ctx.needs_input_grad
+        g_v = api.eval_transpose_device(name, r_trg, r_src, n_src, grad_u, digits=digits, ctx=ctx) if need[4] else None
+        want = [what for what, i in (("trg", 1), ("src", 2), ("nrm", 3)) if need[i]]
+        g_trg = g_src = g_nrm = None
+        if want:
+            g = api.eval_grad_device(name, r_trg, r_src, n_src, v_src, grad_u, want=want, digits=digits, ctx=ctx)
+            g_trg, g_src, g_nrm = [None if x is None else x.view(shape) for x, shape in zip(g, fn_ctx.shapes)]
+        return None, g_trg, g_src, g_nrm, g_v, None, None
+
+
+def kernel_sum_geometry(name, r_trg, r_src, n_src, v_src, digits=-1, ctx=None):
+    """GenericKernel::Eval on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to r_trg, r_src,
+    n_src and v_src.  The backward runs on the forward's stream, as autograd arranges, and is once-differentiable."""
+    return _KernelSumGeometry.apply(name, r_trg, r_src, n_src, v_src, digits, ctx)

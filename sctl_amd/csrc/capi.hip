@@ -218,22 +218,25 @@ int64_t transpose_workspace_cap() {
   const long long v = std::atoll(e);
   return (v >= 1 && v < kTransposeWorkspaceCap) ? (int64_t)v : kTransposeWorkspaceCap;
 }
-PlanT make_plan_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns) {
-  const int64_t rs = (real == SCTL_AMD_F64 ? 8 : 4);
-  const int64_t want = (int64_t)cu_count() * ((double)Nt * (double)Ns < 2147483648.0 ? 4 : 8);
-  PlanT p{};
-  const int t = (Ns >= 32768) ? 2 : 1;
-  p.t_idx = (t == 1) ? 0 : 1;
-  int64_t wg_x = (Ns + (int64_t)kBlock * t - 1) / ((int64_t)kBlock * t);
+// The geometry shared by the owner schemes that stream the other set (the transposed and the gradient evaluators): `owners` points own `out_width` sums
+// each, t per lane; the `streamed` points, `streamed_reals` reals each, are split.
+struct PlanOwned {
+  int splits;
+  int64_t chunk, owners_per_launch, workspace_bytes;
+};
+PlanOwned plan_owned(int64_t owners, int64_t streamed, int t, int64_t streamed_reals, int64_t out_width, int64_t rs) {
+  const int64_t want = (int64_t)cu_count() * ((double)owners * (double)streamed < 2147483648.0 ? 4 : 8);
+  PlanOwned p{};
+  int64_t wg_x = (owners + (int64_t)kBlock * t - 1) / ((int64_t)kBlock * t);
   if (wg_x < 1) wg_x = 1;
-  const int64_t ntile = (Nt + kTile - 1) / kTile;
+  const int64_t ntile = (streamed + kTile - 1) / kTile;
   int64_t s = (want + wg_x - 1) / wg_x;
   if (s > ntile) s = ntile;
   if (s > 1024) s = 1024;
   if (s < 1) s = 1;
-  if ((double)Nt * (double)Ns >= 17179869184.0) {   // one split's streamed data <= 2 MB, splits in eights, at most 64 (make_plan)
-    const int64_t trg_bytes = Nt * (3 + k.k1) * rs;
-    int64_t s2 = (trg_bytes + (2 << 20) - 1) / (2 << 20);
+  if ((double)owners * (double)streamed >= 17179869184.0) {   // one split's streamed data <= 2 MB, splits in eights, at most 64 (make_plan)
+    const int64_t bytes = streamed * streamed_reals * rs;
+    int64_t s2 = (bytes + (2 << 20) - 1) / (2 << 20);
     s2 = (s2 + 7) / 8 * 8;
     if (s2 > 64) s2 = 64;
     if (s2 > s) s = s2;
@@ -243,17 +246,33 @@ PlanT make_plan_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns) {
   int64_t tiles_per = (ntile + s - 1) / s;
   if (tiles_per < 1) tiles_per = 1;
   p.chunk = tiles_per * kTile;
-  p.splits = (int)((Nt + p.chunk - 1) / p.chunk);
+  p.splits = (int)((streamed + p.chunk - 1) / p.chunk);
   if (p.splits < 1) p.splits = 1;
-  p.owners_per_launch = Ns > 0 ? Ns : 1;
+  p.owners_per_launch = owners > 0 ? owners : 1;
   if (p.splits > 1) {
     const int64_t group = (int64_t)kBlock * t;
-    int64_t cap = transpose_workspace_cap() / ((int64_t)p.splits * k.k0 * rs) / group * group;   // >= 2^31 / (1024 * 32 * 8) = 8192 owners
+    int64_t cap = transpose_workspace_cap() / ((int64_t)p.splits * out_width * rs) / group * group;   // >= 2^31 / (1024 * 32 * 8) = 8192 owners
     if (cap < group) cap = group;
     if (p.owners_per_launch > cap) p.owners_per_launch = cap;
   }
-  p.workspace_bytes = (p.splits > 1) ? (int64_t)p.splits * p.owners_per_launch * k.k0 * rs : 0;
+  p.workspace_bytes = (p.splits > 1) ? (int64_t)p.splits * p.owners_per_launch * out_width * rs : 0;
   return p;
+}
+PlanT make_plan_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns) {
+  const int t = (Ns >= 32768) ? 2 : 1;
+  const PlanOwned o = plan_owned(Ns, Nt, t, 3 + k.k1, k.k0, real == SCTL_AMD_F64 ? 8 : 4);
+  PlanT p{};
+  p.t_idx = (t == 1) ? 0 : 1;
+  p.splits = o.splits; p.chunk = o.chunk; p.owners_per_launch = o.owners_per_launch; p.workspace_bytes = o.workspace_bytes;
+  return p;
+}
+// The gradient evaluation (eval_grad_kernel.hpp).  side 0: the targets own 3 sums each and the sources stream as {x, n, f}; side 1: the sources own 3
+// sums, 6 with a normal, and the targets stream as {x, w}.  The owner cut honours the same bound, and the same lowering variable, as the transposed plan.
+int grad_out_width(const KernelEntry& k, int side) { return (side == 1 && k.nd > 0) ? 6 : 3; }
+PlanOwned make_plan_g(const KernelEntry& k, int real, int side, int64_t Nt, int64_t Ns) {
+  const int64_t rs = (real == SCTL_AMD_F64 ? 8 : 4);
+  if (side == 0) return plan_owned(Nt, Ns, k.grad_t[0], 3 + k.nd + k.k0, 3, rs);
+  return plan_owned(Ns, Nt, k.grad_t[1], 3 + k.k1, grad_out_width(k, 1), rs);
 }
 
 int check_common(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
@@ -382,6 +401,65 @@ int eval_transpose_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t 
   }
   g_pairs += Nt * Ns;
   g_flops += Nt * Ns * k.flops;
+  return SCTL_AMD_OK;
+}
+
+bool has_grad(const KernelEntry& k) { return k.grad_t[0] > 0 && k.eval_g_f64[0][0] != nullptr; }
+int no_grad(const KernelEntry& k) {
+  return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, std::string("kernel '") + k.name + "' has no gradient form: its functor supplies no pair_g (device/kernel_plugin.hpp)");
+}
+template <class R> EvalGLaunch<R> pick_eval_g(const KernelEntry& k, int mode, int side);
+template <> EvalGLaunch<double> pick_eval_g<double>(const KernelEntry& k, int mode, int side) { return k.eval_g_f64[mode][side]; }
+template <> EvalGLaunch<float> pick_eval_g<float>(const KernelEntry& k, int mode, int side) { return k.eval_g_f32[mode][side]; }
+
+// One side of the gradient on device arrays, enqueued on st: `owners` points at xo own g (and gn), the other set streams
+template <class R>
+int eval_grad_side(const KernelEntry& k, int real, int side, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, const R* w, R* g, R* gn,
+                   int mode, const void* ctx, hipStream_t st) {
+  const PlanOwned p = make_plan_g(k, real, side, Nt, Ns);
+  const R scale = (R)(k.scale / k.grad_factor[mode]);
+  const int64_t owners = side == 0 ? Nt : Ns;
+  const bool normal = (side == 1 && k.nd > 0);
+  void* ws = nullptr;
+  if (p.splits > 1) HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+  const int64_t group = (int64_t)kBlock * k.grad_t[side];
+  for (int64_t o0 = 0; o0 < owners; o0 += p.owners_per_launch) {   // one launch unless the partial sums of all owners would pass 2 GB
+    const int64_t n = (owners - o0 < p.owners_per_launch) ? owners - o0 : p.owners_per_launch;
+    EvalGArgs<R> a{};
+    a.No = n; a.partial = (R*)ws; a.chunk = p.chunk; a.scale = scale; a.ctx = make_ctx(k, ctx);
+    a.g = g ? g + o0 * 3 : nullptr;
+    a.gn = (normal && gn) ? gn + o0 * 3 : nullptr;
+    if (side == 0) { a.Nst = Ns; a.xo = xt + o0 * 3; a.xst = xs; a.xn = xn; a.f = f; a.w = w + o0 * k.k1; }
+    else { a.Nst = Nt; a.xo = xs + o0 * 3; a.xst = xt; a.xn = xn ? xn + o0 * k.nd : nullptr; a.f = f + o0 * k.k0; a.w = w; }
+    const dim3 grid((unsigned)((n + group - 1) / group), (unsigned)p.splits);
+    pick_eval_g<R>(k, mode, side)(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (p.splits > 1) {
+      const int64_t m = n * 3;
+      const dim3 rgrid((unsigned)((m + kBlock - 1) / kBlock));
+      if (a.g) hipLaunchKernelGGL((reduce_splits_kernel<R>), rgrid, dim3(kBlock), 0, st, a.g, (const R*)a.partial, m, p.splits, scale);
+      if (a.gn) hipLaunchKernelGGL((reduce_splits_kernel<R>), rgrid, dim3(kBlock), 0, st, a.gn, (const R*)a.partial + (int64_t)p.splits * m, m, p.splits, scale);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  g_pairs += Nt * Ns;
+  g_flops += Nt * Ns * k.flops;
+  return SCTL_AMD_OK;
+}
+
+// g_trg, g_src, g_nrm += the gradients of <w, A f> with respect to the target coordinates, the source coordinates and the source normals; a null output is
+// not computed, and a side whose outputs are all null is not launched
+template <class R>
+int eval_grad_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, const R* w, R* g_trg, R* g_src,
+                       R* g_nrm, int digits, const void* ctx, hipStream_t st) {
+  if (Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  (void)hipGetLastError();
+  const int mode = mode_for(real, digits);
+  if (g_trg) {
+    const int rc = eval_grad_side<R>(k, real, 0, Nt, Ns, xt, xs, xn, f, w, g_trg, nullptr, mode, ctx, st);
+    if (rc) return rc;
+  }
+  if (g_src || g_nrm) return eval_grad_side<R>(k, real, 1, Nt, Ns, xt, xs, xn, f, w, g_src, g_nrm, mode, ctx, st);
   return SCTL_AMD_OK;
 }
 
@@ -777,6 +855,16 @@ int sctl_amd_register_kernel(const sctl_amd_kernel_desc* d) {
       for (int t = 0; t < kNumTT; t++) have += (e->eval_t_f64[m][t] != nullptr) + (e->eval_t_f32[m][t] != nullptr);
     if ((have != 0 && have != 2 * kNumMode * kNumTT) || (have != 0) != (e->nrec_t > 0))
       return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete transposed launch table");
+  }
+  {   // ... and so are the gradient launchers (a functor without pair_g)
+    int have = 0;
+    for (int m = 0; m < kNumMode; m++)
+      for (int side = 0; side < 2; side++) have += (e->eval_g_f64[m][side] != nullptr) + (e->eval_g_f32[m][side] != nullptr);
+    const bool named = e->grad_t[0] > 0 && e->grad_t[1] > 0;
+    if ((have != 0 && have != 2 * kNumMode * 2) || (have != 0) != named || (e->grad_t[0] > 0) != (e->grad_t[1] > 0))
+      return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete gradient launch table");
+    for (int m = 0; m < kNumMode && have; m++)
+      if (!(e->grad_factor[m] > 0)) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("kernel '") + d->name + "': incomplete gradient launch table");
   }
   std::string why;
   const int id = registry_add(*e, &why);
@@ -1789,6 +1877,107 @@ int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, i
   if (src_per_lane) *src_per_lane = kTTvalues[p.t_idx];
   if (splits) *splits = p.splits;
   if (workspace_bytes) *workspace_bytes = p.workspace_bytes;
+  return SCTL_AMD_OK;
+}
+
+// ---- gradients of <w_trg, A v_src> with respect to the geometry ------------------------------------------------------------------------
+static int check_grad(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                      const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx) {
+  const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if ((Ns > 0 && !v_src) || (Nt > 0 && !w_trg)) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or weight array");
+  if (g_nrm && k->nd == 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string(k->name) + " has no source normal: g_nrm must be null");
+  if (!has_grad(*k)) return no_grad(*k);
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_grad_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                              const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_grad(k, real, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_nrm, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (device_count_quiet() <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (real == SCTL_AMD_F64)
+    return eval_grad_device_t<double>(*k, real, Nt, Ns, (const double*)r_trg, (const double*)r_src, (const double*)n_src, (const double*)v_src,
+                                      (const double*)w_trg, (double*)g_trg, (double*)g_src, (double*)g_nrm, digits, ctx, (hipStream_t)stream);
+  return eval_grad_device_t<float>(*k, real, Nt, Ns, (const float*)r_trg, (const float*)r_src, (const float*)n_src, (const float*)v_src, (const float*)w_trg,
+                                   (float*)g_trg, (float*)g_src, (float*)g_nrm, digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                            const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int accumulate, int digits, const void* ctx, int ctx_bytes, int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_grad(k, real, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_nrm, ctx_bytes, ctx);
+  if (rc) return rc;
+  const int avail = device_count_quiet();
+  if (avail <= 0) return fail(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
+  if (device < 0 || device >= avail) return fail(SCTL_AMD_ERR_NO_DEVICE, "device index out of range");
+  if (Nt == 0 || Ns == 0) return SCTL_AMD_OK;   // an empty set: nothing is read or written
+  const size_t rs = (real == SCTL_AMD_F64) ? 8 : 4;
+  DeviceScope dev_scope(device);
+  HIP_TRY(dev_scope.err);
+  HostSlot& hs = host_slot(device);
+  if (!hs.st.s) HIP_TRY(hipStreamCreateWithFlags(&hs.st.s, hipStreamNonBlocking));
+  hipStream_t st = hs.st.s;
+  struct Release { HostSlot& h; ~Release() { h.trim((size_t)64 << 20); } } release{hs};
+  // five inputs and up to three outputs, slices of one device block
+  const void* in[5] = {r_trg, r_src, k->nd ? n_src : nullptr, v_src, w_trg};
+  const size_t b_in[5] = {(size_t)Nt * 3 * rs, (size_t)Ns * 3 * rs, (size_t)Ns * k->nd * rs, (size_t)Ns * k->k0 * rs, (size_t)Nt * k->k1 * rs};
+  void* out[3] = {g_trg, g_src, g_nrm};
+  const size_t b_out[3] = {g_trg ? (size_t)Nt * 3 * rs : 0, g_src ? (size_t)Ns * 3 * rs : 0, g_nrm ? (size_t)Ns * 3 * rs : 0};
+  size_t off_in[5], off_out[3], total = 0;
+  for (int i = 0; i < 5; i++) { off_in[i] = total; total += pad256(b_in[i]); }
+  for (int i = 0; i < 3; i++) { off_out[i] = total; total += pad256(b_out[i]); }
+  HIP_TRY(hs.buf[0].reserve(total));
+  HIP_TRY(hs.stage.reserve(total));
+  char* base = (char*)hs.buf[0].p;
+  for (int i = 0; i < 5; i++)
+    if (in[i]) HIP_TRY(upload(base + off_in[i], in[i], b_in[i], hs.stage, st));
+  if (total > off_out[0]) HIP_TRY(hipMemsetAsync(base + off_out[0], 0, total - off_out[0], st));
+  void* dev_out[3];
+  for (int i = 0; i < 3; i++) dev_out[i] = out[i] ? base + off_out[i] : nullptr;
+  void* dn = k->nd ? base + off_in[2] : nullptr;
+  if (real == SCTL_AMD_F64)
+    rc = eval_grad_device_t<double>(*k, real, Nt, Ns, (const double*)(base + off_in[0]), (const double*)(base + off_in[1]), (const double*)dn,
+                                    (const double*)(base + off_in[3]), (const double*)(base + off_in[4]), (double*)dev_out[0], (double*)dev_out[1],
+                                    (double*)dev_out[2], digits, ctx, st);
+  else
+    rc = eval_grad_device_t<float>(*k, real, Nt, Ns, (const float*)(base + off_in[0]), (const float*)(base + off_in[1]), (const float*)dn,
+                                   (const float*)(base + off_in[3]), (const float*)(base + off_in[4]), (float*)dev_out[0], (float*)dev_out[1], (float*)dev_out[2],
+                                   digits, ctx, st);
+  if (rc) return rc;
+  char* back[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; i++)
+    if (out[i]) {
+      back[i] = hs.stage.take(b_out[i]);
+      HIP_TRY(hipMemcpyAsync(back[i], dev_out[i], b_out[i], hipMemcpyDeviceToHost, st));
+    }
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int i = 0; i < 3; i++) {
+    if (!out[i]) continue;
+    const int64_t n = (int64_t)(b_out[i] / rs);
+    if (!accumulate) std::memcpy(out[i], back[i], b_out[i]);
+    else if (real == SCTL_AMD_F64) { double* o = (double*)out[i]; const double* r = (const double*)back[i]; for (int64_t j = 0; j < n; j++) o[j] += r[j]; }
+    else { float* o = (float*)out[i]; const float* r = (const float*)back[i]; for (int64_t j = 0; j < n; j++) o[j] += r[j]; }
+  }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_grad_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* trg_per_lane, int* trg_splits, int64_t* trg_workspace_bytes,
+                            int* src_per_lane, int* src_splits, int64_t* src_workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (!k) return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
+  if (real != SCTL_AMD_F64 && real != SCTL_AMD_F32) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "real must be SCTL_AMD_F64 or SCTL_AMD_F32");
+  if (Nt < 0 || Ns < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative size");
+  if (!has_grad(*k)) return no_grad(*k);
+  (void)digits;   // every accuracy mode runs the same launch geometry
+  const PlanOwned pt = make_plan_g(*k, real, 0, Nt, Ns), ps = make_plan_g(*k, real, 1, Nt, Ns);
+  if (trg_per_lane) *trg_per_lane = k->grad_t[0];
+  if (trg_splits) *trg_splits = pt.splits;
+  if (trg_workspace_bytes) *trg_workspace_bytes = pt.workspace_bytes;
+  if (src_per_lane) *src_per_lane = k->grad_t[1];
+  if (src_splits) *src_splits = ps.splits;
+  if (src_workspace_bytes) *src_workspace_bytes = ps.workspace_bytes;
   return SCTL_AMD_OK;
 }
 

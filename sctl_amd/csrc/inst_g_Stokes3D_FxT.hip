@@ -1,0 +1,5 @@
+// Instantiations of the gradient evaluation kernels for Stokes3D_FxT (see launch.hpp, eval_grad_kernel.hpp).
+#include <sctl_amd/device/launch.hpp>
+namespace sctl_amd {
+SCTL_AMD_EVAL_G_INSTANCES(, Stokes3D_FxT)
+}  // namespace sctl_amd
