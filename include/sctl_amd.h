@@ -383,6 +383,34 @@ int sctl_amd_eval_lists_host(int kernel, int real, int64_t nlists, const int64_t
                              const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                              const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device);
 
+/* ---- the transposed sum over the lists: g_src += A^T w_trg, the adjoint of sctl_amd_lists_eval_* over the same lists ----
+ *     g_src[s*SrcDim + k0] += scale * sum_{l : s in source range l} sum_{t in target range l} sum_k1 U(x_t - x_s, n_s)[k0][k1] * w_trg[t*TrgDim + k1]
+ * with the conventions of sctl_amd_eval_transpose_*: d = x_t - x_s keeps the forward sign, the normal stays with the source, a coincident
+ * pair contributes 0, digits / ctx / scale as in the forward entries, fp32 runs the exact vector-pipe pair; g_src is ACCUMULATED into.
+ * A plan serves the directions it was made for: `directions` is a bit set of SCTL_AMD_LISTS_FORWARD and SCTL_AMD_LISTS_TRANSPOSE
+ * (sctl_amd_lists_create means FORWARD).  The transposed side asks of the SOURCE ranges what the forward side asks of the target ranges:
+ * any two must be IDENTICAL or DISJOINT, so that every source is owned by one wave, its sums run in list order in registers and are
+ * written once — no atomics, no partial-sum workspace, bit-identical results from run to run.  Each direction checks its own rule only:
+ * a TRANSPOSE-only plan may have overlapping target ranges, a FORWARD-only plan overlapping source ranges.  directions of 0 or with an
+ * unknown bit, and evaluating a direction the plan was not made for, are SCTL_AMD_ERR_BAD_ARGUMENT; a kernel without a transposed form
+ * (a plugin functor without pair_t) gets SCTL_AMD_ERR_UNKNOWN_KERNEL from a create that asks for TRANSPOSE.  The counters grow by the
+ * plan's pairs.  _host reuses the handle's stream, staging and device buffers (w_trg has the size of v_trg, g_src that of v_src).
+ * Not built: several densities, geometry gradients and several GPUs over lists. */
+#define SCTL_AMD_LISTS_FORWARD 1
+#define SCTL_AMD_LISTS_TRANSPOSE 2
+int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
+                                     const int64_t* src_off, const int64_t* src_cnt, int64_t Nt, int64_t Ns, int directions, sctl_amd_lists** plan);
+int sctl_amd_lists_eval_transpose_device(sctl_amd_lists* plan, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg, void* g_src,
+                                         int digits, const void* ctx, int ctx_bytes, void* stream);
+int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* plan, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg, void* g_src,
+                                       int digits, const void* ctx, int ctx_bytes);
+/* pair interactions of one transposed evaluation, its work items (waves) and target ranges; all 0 for a FORWARD-only plan.  NULL = skip. */
+int sctl_amd_lists_transpose_info(const sctl_amd_lists* plan, int64_t* pairs, int64_t* work_items, int64_t* target_ranges);
+/* One-shot form (plan TRANSPOSE, evaluate, release), HOST arrays. */
+int sctl_amd_eval_lists_transpose_host(int kernel, int real, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                       const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                       const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, int device);
+
 /* Several densities over the lists of one plan (the several-densities text above applies): density-major v_src[nd][Ns*SrcDim] and
  * v_trg[nd][Nt*TrgDim], every row ACCUMULATED into.  The plan does not depend on nd: one handle serves the single-density entries and any
  * nd.  nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, nd == 1 IS sctl_amd_lists_eval_* (bit-identical results); argument and

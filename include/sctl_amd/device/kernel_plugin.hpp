@@ -42,6 +42,8 @@
 // registers; unused R[1] when ND == 0), the same masking rule, accuracy modes and acc_factor(mode) as pair().  `finish_t<R>(R (&acc)[K0])` /
 // `finish_t_mode<R, MODE>` are the optional counterparts of finish / finish_mode.  Without pair_t the kernel registers and runs as before and
 // the transposed entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for it (tests/plugin/yukawa_kernel.hip has none, yukawa_t_kernel.hip has one).
+// The same three members also give the functor the transposed LIST entries (sctl_amd_lists_eval_transpose_*, lists_transpose_kernel.hpp): make_entry
+// instantiates lists_transpose_kernel in the plugin's own unit; without pair_t a plan that asks for SCTL_AMD_LISTS_TRANSPOSE is UNKNOWN_KERNEL.
 // Optional, the GRADIENT form (sctl_amd_eval_grad_*: the derivatives of <w, A f> with respect to the coordinates of both point sets and the source normals).  A functor
 // that supplies
 //     template <class R, int MODE, bool MASKED, bool WANT_N>

@@ -5,6 +5,7 @@
 #include "eval_transpose_kernel.hpp"
 #include "eval_grad_kernel.hpp"
 #include "lists_kernel.hpp"
+#include "lists_transpose_kernel.hpp"
 
 namespace sctl_amd {
 
@@ -19,6 +20,7 @@ template <class R> using EvalTLaunch = void (*)(const EvalTArgs<R>&, dim3 grid, 
 template <class R> using EvalGLaunch = void (*)(const EvalGArgs<R>&, dim3 grid, hipStream_t);
 template <class R> using MatrixBatchLaunch = void (*)(const MatTile* tiles, int64_t ntiles, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, hipStream_t);
 template <class R> using ListsLaunch = void (*)(const ListArgs<R>&, int64_t nblocks, hipStream_t);
+template <class R> using ListsTLaunch = void (*)(const ListTArgs<R>&, int64_t nblocks, hipStream_t);
 template <class R> using MatrixLaunch = void (*)(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, R* M, R scale, const KerCtx&, dim3 grid, hipStream_t);
 
 struct KernelEntry {
@@ -43,6 +45,10 @@ struct KernelEntry {
   double grad_factor[kNumMode];                     // pair_g() of mode m accumulates grad_factor[m] x the derivative (GradFactorOf)
   EvalGLaunch<double> eval_g_f64[kNumMode][2];
   EvalGLaunch<float> eval_g_f32[kNumMode][2];       // modes 0 and 1 only (mode 2 aliases mode 1)
+  // the transposed list evaluator (lists_transpose_kernel.hpp): null for a functor without pair_t.  At the END of the entry: registration refuses a
+  // plugin built against a shorter entry by entry_bytes, so SCTL_AMD_DEVICE_ABI stays as it is
+  ListsTLaunch<double> lists_t_f64[kNumMode];
+  ListsTLaunch<float> lists_t_f32[kNumMode];        // modes 0 and 1 only (mode 2 aliases mode 1)
 };
 
 // Owners per lane of the gradient evaluator, per kernel and side.  One everywhere: a gradient pair is two to four times the forward pair's arithmetic, so
@@ -73,6 +79,10 @@ template <class Ker, class R, int MODE> void launch_lists(const ListArgs<R>& a, 
   hipLaunchKernelGGL((lists_kernel<Ker, R, MODE>), dim3((unsigned)nblocks), dim3(kListWave), 0, st, a);
 }
 
+template <class Ker, class R, int MODE> void launch_lists_t(const ListTArgs<R>& a, int64_t nblocks, hipStream_t st) {
+  hipLaunchKernelGGL((lists_transpose_kernel<Ker, R, MODE>), dim3((unsigned)nblocks), dim3(kListWave), 0, st, a);
+}
+
 template <class Ker> KernelEntry make_entry(int ctx_bytes) {
   KernelEntry e{};
   e.name = Ker::NAME; e.id = Ker::ID; e.k0 = Ker::K0; e.k1 = Ker::K1; e.nd = Ker::ND; e.flops = Ker::FLOPS; e.nrec = Ker::NREC;
@@ -97,6 +107,8 @@ template <class Ker> KernelEntry make_entry(int ctx_bytes) {
     SCTL_AMD_ROW_T(double, e.eval_t_f64, 0, 0) SCTL_AMD_ROW_T(double, e.eval_t_f64, 1, 1) SCTL_AMD_ROW_T(double, e.eval_t_f64, 2, 2)
     SCTL_AMD_ROW_T(float, e.eval_t_f32, 0, 0) SCTL_AMD_ROW_T(float, e.eval_t_f32, 1, 1) SCTL_AMD_ROW_T(float, e.eval_t_f32, 2, 1)
 #undef SCTL_AMD_ROW_T
+    e.lists_t_f64[0] = launch_lists_t<Ker, double, 0>; e.lists_t_f64[1] = launch_lists_t<Ker, double, 1>; e.lists_t_f64[2] = launch_lists_t<Ker, double, 2>;
+    e.lists_t_f32[0] = launch_lists_t<Ker, float, 0>; e.lists_t_f32[1] = launch_lists_t<Ker, float, 1>; e.lists_t_f32[2] = launch_lists_t<Ker, float, 1>;
   }
   if constexpr (HasPairG<Ker>::value) {
     e.grad_t[0] = GradOwnersOf<Ker, 0>::value; e.grad_t[1] = GradOwnersOf<Ker, 1>::value;
@@ -155,6 +167,24 @@ SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FSxU)
 SCTL_AMD_EVAL_G_INSTANCES(extern, Stokes3D_FxUP)
 SCTL_AMD_EVAL_G_INSTANCES(extern, Laplace3D_FDxUdU)
 SCTL_AMD_EVAL_G_INSTANCES(extern, Helmholtz3D_FxU)
+
+// ... the transposed list launchers in inst_lt_*.hip
+#define SCTL_AMD_LISTS_T_INSTANCES(PREFIX, Ker)                                                             \
+  PREFIX template void launch_lists_t<Ker, double, 0>(const ListTArgs<double>&, int64_t, hipStream_t);      \
+  PREFIX template void launch_lists_t<Ker, double, 1>(const ListTArgs<double>&, int64_t, hipStream_t);      \
+  PREFIX template void launch_lists_t<Ker, double, 2>(const ListTArgs<double>&, int64_t, hipStream_t);      \
+  PREFIX template void launch_lists_t<Ker, float, 0>(const ListTArgs<float>&, int64_t, hipStream_t);        \
+  PREFIX template void launch_lists_t<Ker, float, 1>(const ListTArgs<float>&, int64_t, hipStream_t);
+SCTL_AMD_LISTS_T_INSTANCES(extern, Laplace3D_FxU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Laplace3D_DxU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Laplace3D_FxdU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Stokes3D_FxU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Stokes3D_DxU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Stokes3D_FxT)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Stokes3D_FSxU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Stokes3D_FxUP)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Laplace3D_FDxUdU)
+SCTL_AMD_LISTS_T_INSTANCES(extern, Helmholtz3D_FxU)
 
 // defined in inst_*.hip
 const KernelEntry& entry_Laplace3D_FxU();

@@ -206,6 +206,32 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_transpose_host");
   }
 
+  // EvalTranspose over P2P lists (sctl_amd_eval_lists_transpose_host; not in the reference): g_src += sum over the lists of A_l^T w_trg, the adjoint of
+  // EvalLists over the same lists.  The SOURCE ranges of any two lists must be identical or disjoint; target ranges may overlap.  g_src follows
+  // EvalTranspose's rule: the right size is accumulated into, any other is resized and zeroed.
+  template <class Real, Integer digits = -1>
+  void EvalListsTranspose(Vector<Real>& g_src, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Vector<Real>& w_trg,
+                          const Vector<Long>& trg_off, const Vector<Long>& trg_cnt, const Vector<Long>& src_off, const Vector<Long>& src_cnt) const {
+    static_assert(sizeof(Long) == sizeof(int64_t), "Long must be 64 bits wide");
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nl = trg_off.Dim();
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(w_trg.Dim() == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(trg_cnt.Dim() == nl && src_off.Dim() == nl && src_cnt.Dim() == nl);
+    if (g_src.Dim() != Ns * KDIM0) {
+      g_src.ReInit(Ns * KDIM0);
+      g_src.SetZero();
+    }
+    if (!nl) return;
+    RequireSupported();
+    auto i64 = [](const Vector<Long>& v) { return reinterpret_cast<const int64_t*>(&v[0]); };
+    const int rc = sctl_amd_eval_lists_transpose_host(DeviceKernelId(), RealTag<Real>::value, nl, i64(trg_off), i64(trg_cnt), i64(src_off), i64(src_cnt), Nt, Ns,
+                                                      r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, w_trg.begin(), g_src.begin(), (int)digits,
+                                                      ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_lists_transpose_host");
+  }
+
   // The gradients of L = <w_trg, A v_src> with respect to the geometry (sctl_amd_eval_grad_host; not in the reference): with d = x_t - x_s and
   // phi_ts = sum_k0 sum_k1 w_trg[t*TrgDim + k1] U(d, n_s)[k0][k1] v_src[s*SrcDim + k0],
   //   g_trg[t*DIM + j] += scale sum_s d phi_ts / d d_j,    g_src[s*DIM + j] -= scale sum_t d phi_ts / d d_j,    g_nrm[s*DIM + j] += scale sum_t d phi_ts / d n_j.

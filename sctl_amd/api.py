@@ -32,6 +32,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_densities_plan", "sctl_amd_near_apply_densities_host", "sctl_amd_near_apply_densities_device", "sctl_amd_op_eval_potential_densities",
            "sctl_amd_lists_eval_densities_device", "sctl_amd_lists_eval_densities_host", "sctl_amd_eval_lists_densities_host",
            "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan",
+           "sctl_amd_lists_create_directions", "sctl_amd_lists_eval_transpose_device", "sctl_amd_lists_eval_transpose_host", "sctl_amd_lists_transpose_info",
+           "sctl_amd_eval_lists_transpose_host",
            "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan"]
 
 
@@ -131,6 +133,11 @@ def lib():
     L.sctl_amd_near_apply_densities_device.argtypes = [vp, ci, vp, vp, vp]
     L.sctl_amd_op_eval_potential_densities.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, ci]
     L.sctl_amd_eval_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(i64)] * 2
+    L.sctl_amd_lists_create_directions.argtypes = [ci, ci, ci, i64, vp, vp, vp, vp, i64, i64, ci, C.POINTER(vp)]
+    L.sctl_amd_lists_eval_transpose_device.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_lists_eval_transpose_host.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci]
+    L.sctl_amd_lists_transpose_info.argtypes = [vp, pi64, pi64, pi64]
+    L.sctl_amd_eval_lists_transpose_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_transpose_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -772,25 +779,80 @@ class NearOp:
             pass
 
 
+LISTS_FORWARD, LISTS_TRANSPOSE = 1, 2
+_LISTS_DIRECTIONS = {"forward": LISTS_FORWARD, "transpose": LISTS_TRANSPOSE, "both": LISTS_FORWARD | LISTS_TRANSPOSE}
+
+
 class ListsPlan:
     """Many (target range x source range) direct sums in one launch (sctl_amd_lists_*): the P2P / U-list shape of a tree code
-    (fmm-wrapper.txx:756-786).  Offsets and counts are in points; target ranges must be identical or disjoint."""
+    (fmm-wrapper.txx:756-786).  Offsets and counts are in points.  directions: "forward" (eval_*: target ranges must be identical or
+    disjoint), "transpose" (eval_transpose_*: the same of the source ranges) or "both"."""
 
-    def __init__(self, name, dtype, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, device=0, ctx=None):
+    def __init__(self, name, dtype, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, device=0, ctx=None, directions="forward"):
         self.info = kernel_info(name)
         self.dtype = np.dtype(dtype)
         self.real = _real_of(dtype)
         self.ctx, self.Nt, self.Ns, self.device = ctx, int(Nt), int(Ns), device
+        if directions not in _LISTS_DIRECTIONS:
+            raise SctlAmdError('directions must be "forward", "transpose" or "both"')
+        self.directions = _LISTS_DIRECTIONS[directions]
         arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (trg_off, trg_cnt, src_off, src_cnt)]
         if len({a.size for a in arrs}) != 1:
             raise SctlAmdError("the four list arrays must have one entry per list")
         p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
         self._h = C.c_void_p()
-        _check(lib().sctl_amd_lists_create(self.info["id"], self.real, device, arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), self.Nt, self.Ns,
-                                           C.byref(self._h)), "lists_create")
+        if self.directions == LISTS_FORWARD:
+            _check(lib().sctl_amd_lists_create(self.info["id"], self.real, device, arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), self.Nt, self.Ns,
+                                               C.byref(self._h)), "lists_create")
+        else:
+            _check(lib().sctl_amd_lists_create_directions(self.info["id"], self.real, device, arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), self.Nt,
+                                                          self.Ns, self.directions, C.byref(self._h)), "lists_create_directions")
         v = [C.c_int64() for _ in range(3)]
         _check(lib().sctl_amd_lists_info(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])), "lists_info")
         self.pairs, self.work_items, self.source_ranges = v[0].value, v[1].value, v[2].value
+
+    def transpose_info(self):
+        """pairs, work items and target ranges of the transposed side (sctl_amd_lists_transpose_info); all 0 for a forward-only plan."""
+        v = [C.c_int64() for _ in range(3)]
+        _check(lib().sctl_amd_lists_transpose_info(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])), "lists_transpose_info")
+        return dict(pairs=v[0].value, work_items=v[1].value, target_ranges=v[2].value)
+
+    def eval_transpose_host(self, r_trg, r_src, n_src, w_trg, g_src=None, digits=-1):
+        """g_src += A^T w_trg over the lists on numpy arrays (sctl_amd_lists_eval_transpose_host): w_trg holds Nt*TrgDim target weights; a g_src
+        of Ns*SrcDim values is accumulated into, otherwise a fresh zeroed result is returned."""
+        dt, i = self.dtype, self.info
+        if np.size(w_trg) != self.Nt * i["k1"]:
+            raise SctlAmdError("w_trg must be Nt*TrgDim = %d values" % (self.Nt * i["k1"]))
+        if g_src is None:
+            g_src = np.zeros(self.Ns * i["k0"], dtype=dt)
+        elif g_src.size != self.Ns * i["k0"]:
+            raise SctlAmdError("g_src must be Ns*SrcDim = %d values" % (self.Ns * i["k0"]))
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        _check(lib().sctl_amd_lists_eval_transpose_host(self._h, _np_ptr(r_trg, dt, self.Nt * 3, "r_trg"), _np_ptr(r_src, dt, self.Ns * 3, "r_src"),
+                                                        _np_ptr(n_src, dt, self.Ns * i["nd"], "n_src"), _np_ptr(w_trg, dt, self.Nt * i["k1"], "w_trg"),
+                                                        _np_ptr(g_src, dt, self.Ns * i["k0"], "g_src"), digits, cp, cb), "lists_eval_transpose_host")
+        return g_src
+
+    def eval_transpose_device(self, r_trg, r_src, n_src, w_trg, g_src=None, digits=-1, stream=None):
+        """The same on torch CUDA tensors on the plan's device (sctl_amd_lists_eval_transpose_device), enqueued on `stream` (default: torch's
+        current stream); g_src is accumulated into."""
+        import torch
+        i = self.info
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if w_trg.numel() != self.Nt * i["k1"]:
+            raise SctlAmdError("w_trg must be Nt*TrgDim = %d values" % (self.Nt * i["k1"]))
+        if g_src is None:
+            g_src = torch.zeros(self.Ns * i["k0"], dtype=tdt, device=r_trg.device)
+        elif g_src.numel() != self.Ns * i["k0"]:
+            raise SctlAmdError("g_src must be Ns*SrcDim = %d values" % (self.Ns * i["k0"]))
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        with torch.cuda.device(r_trg.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_lists_eval_transpose_device(self._h, _t_ptr(r_trg, tdt, self.Nt * 3, "r_trg"), _t_ptr(r_src, tdt, self.Ns * 3, "r_src"),
+                                                              _t_ptr(n_src, tdt, self.Ns * i["nd"], "n_src"), _t_ptr(w_trg, tdt, self.Nt * i["k1"], "w_trg"),
+                                                              _t_ptr(g_src, tdt, self.Ns * i["k0"], "g_src"), digits, cp, cb, C.c_void_p(st.cuda_stream)),
+                   "lists_eval_transpose_device")
+        return g_src
 
     def eval_host(self, r_trg, r_src, n_src, v_src, v_trg=None, digits=-1):
         """numpy arrays; v_trg of the right size is accumulated into, otherwise a fresh zeroed result is returned."""
@@ -896,3 +958,12 @@ def eval_lists_densities_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r
                                                     _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(F, dt, nd * Ns * info["k0"], "F"),
                                                     _np_ptr(V_trg, dt, nd * Nt * info["k1"], "V_trg"), digits, cp, cb, device), "eval_lists_densities_host")
     return V_trg
+
+
+def eval_lists_transpose_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, w_trg, g_src=None, digits=-1, ctx=None, device=0):
+    """One-shot sctl_amd_eval_lists_transpose_host: a plan of the transposed side only, evaluated once and released."""
+    plan = ListsPlan(name, r_trg.dtype, trg_off, trg_cnt, src_off, src_cnt, r_trg.size // 3, r_src.size // 3, device=device, ctx=ctx, directions="transpose")
+    try:
+        return plan.eval_transpose_host(r_trg, r_src, n_src, w_trg, g_src, digits)
+    finally:
+        plan.close()

@@ -9,7 +9,14 @@ kernel_sum_geometry differentiates the geometry as well: its backward adds sctl_
 of r_trg, r_src, n_src need a gradient.
 
     u = sctl_amd.autograd.kernel_sum_geometry("Laplace3D-DxU", r_trg, r_src, n_src, v_src)   # any of the four may require grad
-    u.square().sum().backward()                                                               # r_trg.grad, r_src.grad, n_src.grad, v_src.grad"""
+    u.square().sum().backward()                                                               # r_trg.grad, r_src.grad, n_src.grad, v_src.grad
+
+lists_sum is kernel_sum over the P2P lists of a ListsPlan made with directions="both": the forward is plan.eval_device, the backward
+plan.eval_transpose_device; densities only.
+
+    plan = sctl_amd.ListsPlan("Stokes3D-FxU", np.float64, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, directions="both")
+    u = sctl_amd.autograd.lists_sum(plan, r_trg, r_src, None, v_src)
+    u.square().sum().backward()                                                      # v_src.grad = sum over the lists of A_l^T (2 u)"""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -75,3 +82,32 @@ def kernel_sum_geometry(name, r_trg, r_src, n_src, v_src, digits=-1, ctx=None):
     """GenericKernel::Eval on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to r_trg, r_src,
     n_src and v_src.  The backward runs on the forward's stream, as autograd arranges, and is once-differentiable."""
     return _KernelSumGeometry.apply(name, r_trg, r_src, n_src, v_src, digits, ctx)
+
+
+class _ListsSum(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, plan, r_trg, r_src, n_src, v_src, digits):
+        fn_ctx.plan, fn_ctx.digits = plan, digits
+        fn_ctx.save_for_backward(r_trg, r_src, n_src)
+        return plan.eval_device(r_trg.detach(), r_src.detach(), None if n_src is None else n_src.detach(), v_src.detach().contiguous(), digits=digits)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_u):
+        r_trg, r_src, n_src = fn_ctx.saved_tensors
+        g = None
+        if fn_ctx.needs_input_grad[4]:
+            g = fn_ctx.plan.eval_transpose_device(r_trg, r_src, n_src, grad_u.contiguous(), digits=fn_ctx.digits)
+        return None, None, None, None, g, None
+
+
+def lists_sum(plan, r_trg, r_src, n_src, v_src, digits=-1):
+    """plan.eval_device on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to v_src: the backward is
+    plan.eval_transpose_device on the forward's stream, as autograd arranges, and is once-differentiable.  The plan must hold both directions."""
+    both = api.LISTS_FORWARD | api.LISTS_TRANSPOSE
+    if plan.directions != both:
+        raise api.SctlAmdError('lists_sum needs a ListsPlan made with directions="both": the backward pass is the transposed list sum')
+    for what, t in (("r_trg", r_trg), ("r_src", r_src), ("n_src", n_src)):
+        if t is not None and t.requires_grad:
+            raise api.SctlAmdError("lists_sum differentiates with respect to the densities only: %s requires grad" % what)
+    return _ListsSum.apply(plan, r_trg, r_src, n_src, v_src, digits)

@@ -1,0 +1,5 @@
+// Instantiations of the transposed list kernels for Laplace3D_FDxUdU (see launch.hpp, lists_transpose_kernel.hpp).
+#include <sctl_amd/device/launch.hpp>
+namespace sctl_amd {
+SCTL_AMD_LISTS_T_INSTANCES(, Laplace3D_FDxUdU)
+}  // namespace sctl_amd

@@ -1,0 +1,5 @@
+// Instantiations of the transposed list kernels for Stokes3D_FxU (see launch.hpp, lists_transpose_kernel.hpp).
+#include <sctl_amd/device/launch.hpp>
+namespace sctl_amd {
+SCTL_AMD_LISTS_T_INSTANCES(, Stokes3D_FxU)
+}  // namespace sctl_amd

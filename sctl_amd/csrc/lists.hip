@@ -22,13 +22,20 @@ namespace {
 }  // namespace
 }  // namespace sctl_amd
 
+// The work list of one direction.  FORWARD: the owners are the targets and the sources are streamed (lists_kernel.hpp); TRANSPOSE: the owners are the sources and
+// the targets are streamed (lists_transpose_kernel.hpp).  Both are made by the same planning code (plan_side) with the two point sets exchanged.
+struct ListsSide {
+  int64_t nitems = 0, nranges = 0, pairs = 0, nblocks = 0;
+  int32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  void *d_items = nullptr, *d_ranges = nullptr, *d_groups = nullptr, *d_flat = nullptr;   // (groups + flat indices of the streamed points: the packed small owner ranges)
+  int64_t npacked_groups = 0, nflat = 0;
+};
+
 struct sctl_amd_lists {
   const sctl_amd::KernelEntry* k = nullptr;
-  int real = 0, device = 0;
-  int64_t Nt = 0, Ns = 0, nitems = 0, nranges = 0, pairs = 0, nblocks = 0;
-  int32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  void *d_items = nullptr, *d_ranges = nullptr, *d_groups = nullptr, *d_flat = nullptr;   // (groups + flat source indices: the packed small target ranges)
-  int64_t npacked_groups = 0, nflat = 0;
+  int real = 0, device = 0, directions = 0;
+  int64_t Nt = 0, Ns = 0;
+  ListsSide side[2];      // [0] FORWARD, [1] TRANSPOSE; a side that was not planned stays empty
   // host-pointer evaluation: device copies of the caller's arrays and pinned staging, grown on demand
   hipStream_t st = nullptr;
   void* dbuf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -38,64 +45,65 @@ struct sctl_amd_lists {
 };
 
 using namespace sctl_amd;
-// Target ranges of up to this many points are packed, several to a wave (lists_kernel.hpp); larger ones keep a wave (or several) to themselves.  Measured on
+// Owner ranges of up to this many points are packed, several to a wave (lists_kernel.hpp); larger ones keep a wave (or several) to themselves.  Measured on
 // 2^21 points in g^3 boxes, every box against its 27 neighbours (tools/time_lists.py, profiles/r04_time_lists_classes.txt; Laplace / Stokeslet, % of the fp64
 // peak, packing up to 0 | 8 | 16 | 32 | 64 points): ~8 per box 4.4 | 6.6 | 11.2 | 11.3 | 11.0 and 11.7 | 15.8 | 23.7 | 23.9 | 23.6; ~11 per box 7.3 | 7.7 | 11.5 |
 // 12.9 | 12.8; ~24 per box 12.0 | 11.9 | 11.8 | 15.5 | 15.5; ~64 per box 21.1 | 20.9 | 20.9 | 20.7 | 18.3 and 45.7 | 46.5 | 46.0 | 46.0 | 40.6: 32.
 constexpr int64_t kPackUpTo = 32;
 
-extern "C" {
+namespace {
+// One side's work list on the host, before it goes to the device
+struct SidePlan {
+  std::vector<ListItem> items;
+  std::vector<ListRange> ranges;
+  std::vector<PackedGroup> pgroups;
+  std::vector<uint32_t> flat;
+  int32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t pairs = 0, longest = 0;
+};
 
-int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
-                          const int64_t* src_cnt, int64_t Nt, int64_t Ns, sctl_amd_lists** out) {
-  const KernelEntry* k = registry(kernel);
-  if (!k) return set_error(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
-  if (real != SCTL_AMD_F64 && real != SCTL_AMD_F32) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "real must be SCTL_AMD_F64 or SCTL_AMD_F32");
-  if (!out || nlists < 0 || Nt < 0 || Ns < 0 || (nlists > 0 && (!trg_off || !trg_cnt || !src_off || !src_cnt)))
-    return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle pointer, negative size or null list arrays");
-  for (int64_t l = 0; l < nlists; l++) {
-    if (trg_cnt[l] < 0 || src_cnt[l] < 0 || trg_off[l] < 0 || src_off[l] < 0 || trg_off[l] + trg_cnt[l] > Nt || src_off[l] + src_cnt[l] > Ns)
-      return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "list " + std::to_string(l) + " reaches outside the target or source arrays");
-  }
-  // group the lists by target range: stable sort by (first target, count) keeps the caller's order inside a group, which is
-  // the order the sources are summed in
+// Plans one side: the lists grouped by OWNER range (own_off, own_cnt), the other point set STREAMED (str_off, str_cnt; Nstr points, each at most
+// `widest` bytes in the widest of its arrays).  `owner` / `streamed` name the two sets in messages ("target" / "source" forward, exchanged transposed).
+int plan_side(int64_t nlists, const int64_t* own_off, const int64_t* own_cnt, const int64_t* str_off, const int64_t* str_cnt, int64_t Nstr, int64_t widest,
+              const char* owner, SidePlan& out) {
+  // group the lists by owner range: stable sort by (first owner, count) keeps the caller's order inside a group, which is
+  // the order the streamed points are summed in
   std::vector<int64_t> order;
   order.reserve((size_t)nlists);
   for (int64_t l = 0; l < nlists; l++)
-    if (trg_cnt[l] > 0 && src_cnt[l] > 0) order.push_back(l);
-  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return trg_off[a] != trg_off[b] ? trg_off[a] < trg_off[b] : trg_cnt[a] < trg_cnt[b]; });
+    if (own_cnt[l] > 0 && str_cnt[l] > 0) order.push_back(l);
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return own_off[a] != own_off[b] ? own_off[a] < own_off[b] : own_cnt[a] < own_cnt[b]; });
   struct Group { int64_t t0, nt, first_range, nranges, nsrc; };
   std::vector<Group> groups;
-  std::vector<ListRange> ranges;
+  std::vector<ListRange>& ranges = out.ranges;
   ranges.reserve(order.size());
   int64_t pairs = 0;
   for (size_t i = 0; i < order.size(); i++) {
     const int64_t l = order[i];
-    if (groups.empty() || groups.back().t0 != trg_off[l] || groups.back().nt != trg_cnt[l]) {
-      if (!groups.empty() && trg_off[l] < groups.back().t0 + groups.back().nt)
-        return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "the target ranges of lists " + std::to_string(order[i - 1]) + " and " + std::to_string(l) +
-                                                        " overlap without being equal: target ranges must be identical or disjoint");
-      groups.push_back(Group{trg_off[l], trg_cnt[l], (int64_t)ranges.size(), 0, 0});
+    if (groups.empty() || groups.back().t0 != own_off[l] || groups.back().nt != own_cnt[l]) {
+      if (!groups.empty() && own_off[l] < groups.back().t0 + groups.back().nt)
+        return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("the ") + owner + " ranges of lists " + std::to_string(order[i - 1]) + " and " + std::to_string(l) +
+                                                        " overlap without being equal: " + owner + " ranges must be identical or disjoint");
+      groups.push_back(Group{own_off[l], own_cnt[l], (int64_t)ranges.size(), 0, 0});
     }
-    ranges.push_back(ListRange{src_off[l], src_cnt[l]});
+    ranges.push_back(ListRange{str_off[l], str_cnt[l]});
     groups.back().nranges++;
-    groups.back().nsrc += src_cnt[l];
-    pairs += trg_cnt[l] * src_cnt[l];
+    groups.back().nsrc += str_cnt[l];
+    pairs += own_cnt[l] * str_cnt[l];
   }
   for (const Group& g : groups)
-    if (g.nranges > INT32_MAX) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "too many lists for one target range");
-  // Eight shares, one per XCD (lists_kernel.hpp): contiguous runs of target ranges in the caller's order — a tree code lists its
-  // boxes along a space-filling curve, so a run is a compact region whose boxes stream the same sources — each with 1/8 of the
-  // pair count.  Inside a share: long items first (a short tail), coarsely — by the number of 4096-source chunks —, neighbours
+    if (g.nranges > INT32_MAX) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, std::string("too many lists for one ") + owner + " range");
+  // Eight shares, one per XCD (lists_kernel.hpp): contiguous runs of owner ranges in the caller's order — a tree code lists its
+  // boxes along a space-filling curve, so a run is a compact region whose boxes stream the same points — each with 1/8 of the
+  // pair count.  Inside a share: long items first (a short tail), coarsely — by the number of 4096-point chunks —, neighbours
   // otherwise staying neighbours.
-  std::vector<ListItem> items;
-  std::vector<PackedGroup> pgroups;
-  std::vector<uint32_t> flat;
-  // The packed form keeps one 32-bit source index per (small target range, source): it is used while that list stays below 2^30 entries (4 GB) and the
-  // sources can be indexed with 32 bits; SCTL_AMD_LISTS_PACK=0 keeps every range on the one-range-per-wave items (A/B runs, tests of that path)
-  // (and while every source array stays under 4 GB: the packed items address a source by a 32-bit byte offset)
-  const int64_t widest = (int64_t)(real == SCTL_AMD_F64 ? 8 : 4) * std::max<int64_t>(3, std::max<int64_t>(k->nd, k->k0));
-  bool pack_small = Ns <= (int64_t)UINT32_MAX / widest;
+  std::vector<ListItem>& items = out.items;
+  std::vector<PackedGroup>& pgroups = out.pgroups;
+  std::vector<uint32_t>& flat = out.flat;
+  // The packed form keeps one 32-bit index per (small owner range, streamed point): it is used while that list stays below 2^30 entries (4 GB) and the
+  // streamed points can be indexed with 32 bits; SCTL_AMD_LISTS_PACK=0 keeps every range on the one-range-per-wave items (A/B runs, tests of that path)
+  // (and while every streamed array stays under 4 GB: the packed items address a streamed point by a 32-bit byte offset)
+  bool pack_small = Nstr <= (int64_t)UINT32_MAX / widest;
   int64_t pack_upto = kPackUpTo;
   if (const char* e = std::getenv("SCTL_AMD_LISTS_PACK")) pack_upto = std::min<int64_t>(64, std::atoi(e));   // (0: off; 8 / 16 / 32 / 64: the largest packed range)
   pack_small = pack_small && pack_upto > 0;
@@ -106,7 +114,7 @@ int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, cons
     if (entries > ((int64_t)1 << 30)) pack_small = false;
     else flat.reserve((size_t)entries);
   }
-  int32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t* const xcd_first = out.xcd_first;
   {
     size_t g0 = 0;
     int64_t done = 0;
@@ -117,8 +125,8 @@ int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, cons
       std::vector<size_t> gorder(g1 - g0);
       std::iota(gorder.begin(), gorder.end(), g0);
       std::stable_sort(gorder.begin(), gorder.end(), [&](size_t a, size_t b) { return (groups[a].nsrc >> 12) > (groups[b].nsrc >> 12); });
-      // Small target ranges (<= 64 points) are PACKED (lists_kernel.hpp): those of one class (lanes x targets per lane) share waves, 64 / P at a time, in
-      // the share's order — neighbours along the caller's space-filling curve —, each with its flat source sequence.  They follow the share's larger items.
+      // Small owner ranges (<= 64 points) are PACKED (lists_kernel.hpp): those of one class (lanes x owners per lane) share waves, 64 / P at a time, in
+      // the share's order — neighbours along the caller's space-filling curve —, each with its flat sequence.  They follow the share's larger items.
       std::vector<size_t> small[4];
       for (size_t gi : gorder) {
         const Group& g = groups[gi];
@@ -126,8 +134,8 @@ int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, cons
           small[g.nt <= 8 ? 0 : g.nt <= 16 ? 1 : g.nt <= 32 ? 2 : 3].push_back(gi);
           continue;
         }
-        // 128-target items (two targets per lane: half the LDS reads per pair); the remainder: more than 96 -> one more such item,
-        // 65..96 -> a one-target-per-lane item of 64 plus a small one, up to 64 -> one item (up to 32: run as lane replicas)
+        // 128-owner items (two owners per lane: half the LDS reads per pair); the remainder: more than 96 -> one more such item,
+        // 65..96 -> a one-owner-per-lane item of 64 plus a small one, up to 64 -> one item (up to 32: run as lane replicas)
         for (int64_t t = 0; t < g.nt;) {
           const int64_t left = g.nt - t;
           const int64_t n = left > 96 ? std::min<int64_t>(left, 2 * kListWave) : (left > kListWave ? kListWave : left);
@@ -154,14 +162,53 @@ int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, cons
   int64_t longest = 0;
   for (int x = 0; x < 8; x++) longest = std::max<int64_t>(longest, xcd_first[x + 1] - xcd_first[x]);
   if (longest * 8 > 0x7fffffff) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "too many work items for one launch");
+  out.pairs = pairs;
+  out.longest = longest;
+  return SCTL_AMD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                     const int64_t* src_cnt, int64_t Nt, int64_t Ns, int directions, sctl_amd_lists** out) {
+  const KernelEntry* k = registry(kernel);
+  if (!k) return set_error(SCTL_AMD_ERR_UNKNOWN_KERNEL, "unknown kernel id");
+  if (real != SCTL_AMD_F64 && real != SCTL_AMD_F32) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "real must be SCTL_AMD_F64 or SCTL_AMD_F32");
+  if (directions == 0 || (directions & ~(SCTL_AMD_LISTS_FORWARD | SCTL_AMD_LISTS_TRANSPOSE)) != 0)
+    return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "directions must be SCTL_AMD_LISTS_FORWARD, SCTL_AMD_LISTS_TRANSPOSE or both");
+  if ((directions & SCTL_AMD_LISTS_TRANSPOSE) && !k->lists_t_f64[0])
+    return set_error(SCTL_AMD_ERR_UNKNOWN_KERNEL, std::string(k->name) + " has no transposed form (pair_t): its lists can be planned FORWARD only");
+  if (!out || nlists < 0 || Nt < 0 || Ns < 0 || (nlists > 0 && (!trg_off || !trg_cnt || !src_off || !src_cnt)))
+    return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle pointer, negative size or null list arrays");
+  for (int64_t l = 0; l < nlists; l++) {
+    if (trg_cnt[l] < 0 || src_cnt[l] < 0 || trg_off[l] < 0 || src_off[l] < 0 || trg_off[l] + trg_cnt[l] > Nt || src_off[l] + src_cnt[l] > Ns)
+      return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "list " + std::to_string(l) + " reaches outside the target or source arrays");
+  }
+  // Each direction checks its own ownership rule only.  The streamed arrays of the forward side are r_src, n_src and v_src, those of the transposed side
+  // r_trg and w_trg: the widest of them bounds the 32-bit byte offsets of the packed form.
+  const int64_t rs = real == SCTL_AMD_F64 ? 8 : 4;
+  SidePlan plans[2];
+  if (directions & SCTL_AMD_LISTS_FORWARD) {
+    const int rc = plan_side(nlists, trg_off, trg_cnt, src_off, src_cnt, Ns, rs * std::max<int64_t>(3, std::max<int64_t>(k->nd, k->k0)), "target", plans[0]);
+    if (rc) return rc;
+  }
+  if (directions & SCTL_AMD_LISTS_TRANSPOSE) {
+    const int rc = plan_side(nlists, src_off, src_cnt, trg_off, trg_cnt, Nt, rs * std::max<int64_t>(3, k->k1), "source", plans[1]);
+    if (rc) return rc;
+  }
 
   sctl_amd_lists* p = new sctl_amd_lists;
-  p->k = k; p->real = real; p->device = device; p->Nt = Nt; p->Ns = Ns;
-  p->nitems = (int64_t)items.size(); p->nranges = (int64_t)ranges.size(); p->pairs = pairs; p->nblocks = longest * 8;
-  p->npacked_groups = (int64_t)pgroups.size(); p->nflat = (int64_t)flat.size();
-  std::memcpy(p->xcd_first, xcd_first, sizeof xcd_first);
+  p->k = k; p->real = real; p->device = device; p->Nt = Nt; p->Ns = Ns; p->directions = directions;
+  for (int d = 0; d < 2; d++) {
+    ListsSide& sd = p->side[d];
+    const SidePlan& pl = plans[d];
+    sd.nitems = (int64_t)pl.items.size(); sd.nranges = (int64_t)pl.ranges.size(); sd.pairs = pl.pairs; sd.nblocks = pl.longest * 8;
+    sd.npacked_groups = (int64_t)pl.pgroups.size(); sd.nflat = (int64_t)pl.flat.size();
+    std::memcpy(sd.xcd_first, pl.xcd_first, sizeof sd.xcd_first);
+  }
   *out = p;
-  if (items.empty()) return SCTL_AMD_OK;       // nothing to do: legal, and needs no device
+  if (plans[0].items.empty() && plans[1].items.empty()) return SCTL_AMD_OK;       // nothing to do: legal, and needs no device
   const int avail = device_count_quiet();
   if (avail <= 0) { delete p; *out = nullptr; return set_error(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback"); }
   if (device < 0 || device >= avail) { delete p; *out = nullptr; return set_error(SCTL_AMD_ERR_NO_DEVICE, "device index out of range"); }
@@ -172,28 +219,43 @@ int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, cons
     return set_error(SCTL_AMD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   };
   if (scope.err != hipSuccess) return fail_hip(scope.err, "hipSetDevice");
-  hipError_t e;
-  if ((e = hipMalloc(&p->d_items, items.size() * sizeof(ListItem))) != hipSuccess) return fail_hip(e, "hipMalloc(items)");
-  if ((e = hipMalloc(&p->d_ranges, ranges.size() * sizeof(ListRange))) != hipSuccess) return fail_hip(e, "hipMalloc(ranges)");
-  // the vectors are fresh, written once and alive until the synchronous copies return
-  if ((e = hipMemcpy(p->d_items, items.data(), items.size() * sizeof(ListItem), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(items)");
-  if ((e = hipMemcpy(p->d_ranges, ranges.data(), ranges.size() * sizeof(ListRange), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(ranges)");
-  if (!pgroups.empty()) {
-    if ((e = hipMalloc(&p->d_groups, pgroups.size() * sizeof(PackedGroup))) != hipSuccess) return fail_hip(e, "hipMalloc(groups)");
-    if ((e = hipMalloc(&p->d_flat, flat.size() * sizeof(uint32_t))) != hipSuccess) return fail_hip(e, "hipMalloc(flat)");
-    if ((e = hipMemcpy(p->d_groups, pgroups.data(), pgroups.size() * sizeof(PackedGroup), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(groups)");
-    if ((e = hipMemcpy(p->d_flat, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(flat)");
+  for (int d = 0; d < 2; d++) {
+    ListsSide& sd = p->side[d];
+    const SidePlan& pl = plans[d];
+    if (pl.items.empty()) continue;
+    hipError_t e;
+    if ((e = hipMalloc(&sd.d_items, pl.items.size() * sizeof(ListItem))) != hipSuccess) return fail_hip(e, "hipMalloc(items)");
+    if ((e = hipMalloc(&sd.d_ranges, pl.ranges.size() * sizeof(ListRange))) != hipSuccess) return fail_hip(e, "hipMalloc(ranges)");
+    // the vectors are fresh, written once and alive until the synchronous copies return
+    if ((e = hipMemcpy(sd.d_items, pl.items.data(), pl.items.size() * sizeof(ListItem), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(items)");
+    if ((e = hipMemcpy(sd.d_ranges, pl.ranges.data(), pl.ranges.size() * sizeof(ListRange), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(ranges)");
+    if (!pl.pgroups.empty()) {
+      if ((e = hipMalloc(&sd.d_groups, pl.pgroups.size() * sizeof(PackedGroup))) != hipSuccess) return fail_hip(e, "hipMalloc(groups)");
+      if ((e = hipMalloc(&sd.d_flat, pl.flat.size() * sizeof(uint32_t))) != hipSuccess) return fail_hip(e, "hipMalloc(flat)");
+      if ((e = hipMemcpy(sd.d_groups, pl.pgroups.data(), pl.pgroups.size() * sizeof(PackedGroup), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(groups)");
+      if ((e = hipMemcpy(sd.d_flat, pl.flat.data(), pl.flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy(flat)");
+    }
   }
   return SCTL_AMD_OK;
 }
 
+int sctl_amd_lists_create(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                          const int64_t* src_cnt, int64_t Nt, int64_t Ns, sctl_amd_lists** out) {
+  return sctl_amd_lists_create_directions(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, SCTL_AMD_LISTS_FORWARD, out);
+}
+
 void sctl_amd_lists_destroy(sctl_amd_lists* p) {
   if (!p) return;
-  if (p->d_items || p->d_ranges || p->d_groups || p->d_flat || p->st || p->pinned) {
+  bool on_device = p->st || p->pinned;
+  for (const ListsSide& sd : p->side) on_device = on_device || sd.d_items || sd.d_ranges || sd.d_groups || sd.d_flat;
+  if (on_device) {
     DeviceScope scope(p->device);
     if (scope.err == hipSuccess) {
       if (p->st) (void)hipStreamSynchronize(p->st);
-      for (void* b : {p->d_items, p->d_ranges, p->d_groups, p->d_flat, p->dbuf[0], p->dbuf[1], p->dbuf[2], p->dbuf[3], p->dbuf[4]})
+      for (const ListsSide& sd : p->side)
+        for (void* b : {sd.d_items, sd.d_ranges, sd.d_groups, sd.d_flat})
+          if (b) (void)hipFree(b);
+      for (void* b : p->dbuf)
         if (b) (void)hipFree(b);
       if (p->pinned) (void)hipHostFree(p->pinned);
       if (p->st) (void)hipStreamDestroy(p->st);
@@ -204,19 +266,29 @@ void sctl_amd_lists_destroy(sctl_amd_lists* p) {
 
 int sctl_amd_lists_info(const sctl_amd_lists* p, int64_t* pairs, int64_t* work_items, int64_t* source_ranges) {
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
-  if (pairs) *pairs = p->pairs;
-  if (work_items) *work_items = p->nitems;
-  if (source_ranges) *source_ranges = p->nranges;
+  if (pairs) *pairs = p->side[0].pairs;
+  if (work_items) *work_items = p->side[0].nitems;
+  if (source_ranges) *source_ranges = p->side[0].nranges;
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_lists_transpose_info(const sctl_amd_lists* p, int64_t* pairs, int64_t* work_items, int64_t* target_ranges) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (pairs) *pairs = p->side[1].pairs;
+  if (work_items) *work_items = p->side[1].nitems;
+  if (target_ranges) *target_ranges = p->side[1].nranges;
   return SCTL_AMD_OK;
 }
 
 int sctl_amd_lists_eval_device(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, void* v_trg, int digits,
                                const void* ctx, int ctx_bytes, void* stream) {
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
+  const ListsSide& fw = p->side[0];
   const KernelEntry& k = *p->k;
   if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
     return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
-  if (p->nitems == 0) return SCTL_AMD_OK;
+  if (p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device: launch there whatever the caller's current device is
   LISTS_TRY(scope.err);
@@ -224,28 +296,29 @@ int sctl_amd_lists_eval_device(sctl_amd_lists* p, const void* r_trg, const void*
   const int mode = mode_for(p->real, digits);
   const double scale = k.scale / k.acc_factor[mode];
   if (p->real == SCTL_AMD_F64) {
-    ListArgs<double> a{{0}, (const ListItem*)p->d_items, (const ListRange*)p->d_ranges, (const double*)r_trg, (const double*)r_src, (const double*)n_src,
-                       (const double*)v_src, (double*)v_trg, scale, make_ctx(k, ctx), (const PackedGroup*)p->d_groups, (const uint32_t*)p->d_flat};
-    std::memcpy(a.xcd_first, p->xcd_first, sizeof a.xcd_first);
-    k.lists_f64[mode](a, p->nblocks, (hipStream_t)stream);
+    ListArgs<double> a{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, (const double*)r_trg, (const double*)r_src, (const double*)n_src,
+                       (const double*)v_src, (double*)v_trg, scale, make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
+    std::memcpy(a.xcd_first, fw.xcd_first, sizeof a.xcd_first);
+    k.lists_f64[mode](a, fw.nblocks, (hipStream_t)stream);
   } else {
-    ListArgs<float> a{{0}, (const ListItem*)p->d_items, (const ListRange*)p->d_ranges, (const float*)r_trg, (const float*)r_src, (const float*)n_src,
-                      (const float*)v_src, (float*)v_trg, (float)scale, make_ctx(k, ctx), (const PackedGroup*)p->d_groups, (const uint32_t*)p->d_flat};
-    std::memcpy(a.xcd_first, p->xcd_first, sizeof a.xcd_first);
-    k.lists_f32[mode](a, p->nblocks, (hipStream_t)stream);
+    ListArgs<float> a{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, (const float*)r_trg, (const float*)r_src, (const float*)n_src,
+                      (const float*)v_src, (float*)v_trg, (float)scale, make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
+    std::memcpy(a.xcd_first, fw.xcd_first, sizeof a.xcd_first);
+    k.lists_f32[mode](a, fw.nblocks, (hipStream_t)stream);
   }
   LISTS_TRY(hipGetLastError());
-  count_work(p->pairs, k);
+  count_work(fw.pairs, k);
   return SCTL_AMD_OK;
 }
 
 int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, void* v_trg, int digits,
                              const void* ctx, int ctx_bytes) {
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
   const KernelEntry& k = *p->k;
   if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
     return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
-  if (p->nitems == 0) return SCTL_AMD_OK;
+  if (p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
   const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
@@ -288,6 +361,104 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
   return SCTL_AMD_OK;
 }
 
+// ---- the transposed sum over the lists (sctl_amd_lists_eval_transpose_*, lists_transpose_kernel.hpp) -----------------------------------
+// g_src += A^T w_trg over the plan's lists, from the side of the plan whose work items own sources.  Checks and their order are those of
+// sctl_amd_lists_eval_*; w_trg has the size of v_trg and g_src the size of v_src, so the handle's device buffers and staging serve both directions.
+int sctl_amd_lists_eval_transpose_device(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg, void* g_src, int digits,
+                                         const void* ctx, int ctx_bytes, void* stream) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
+  const ListsSide& tr = p->side[1];
+  const KernelEntry& k = *p->k;
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (tr.nitems == 0) return SCTL_AMD_OK;
+  if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  (void)hipGetLastError();
+  const int mode = mode_for(p->real, digits);
+  const double scale = k.scale / k.acc_factor[mode];
+  if (p->real == SCTL_AMD_F64) {
+    ListTArgs<double> a{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, (const double*)r_src, (const double*)n_src, (const double*)r_trg,
+                        (const double*)w_trg, (double*)g_src, scale, make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
+    std::memcpy(a.xcd_first, tr.xcd_first, sizeof a.xcd_first);
+    k.lists_t_f64[mode](a, tr.nblocks, (hipStream_t)stream);
+  } else {
+    ListTArgs<float> a{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, (const float*)r_src, (const float*)n_src, (const float*)r_trg,
+                       (const float*)w_trg, (float*)g_src, (float)scale, make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
+    std::memcpy(a.xcd_first, tr.xcd_first, sizeof a.xcd_first);
+    k.lists_t_f32[mode](a, tr.nblocks, (hipStream_t)stream);
+  }
+  LISTS_TRY(hipGetLastError());
+  count_work(tr.pairs, k);
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg, void* g_src, int digits,
+                                       const void* ctx, int ctx_bytes) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
+  const KernelEntry& k = *p->k;
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (p->side[1].nitems == 0) return SCTL_AMD_OK;
+  if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
+  const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
+  // the forward entry's buffers with the roles of the last two exchanged: [3] (the size of v_src) receives g_src, [4] (the size of v_trg) holds w_trg
+  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
+  const void* src[5] = {r_trg, r_src, n_src, nullptr, w_trg};
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  size_t total = 0;
+  for (int i = 0; i < 5; i++) {
+    total += Carver::pad(bytes[i]);
+    if (bytes[i] > p->dcap[i]) {
+      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
+      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
+      p->dcap[i] = bytes[i];
+    }
+  }
+  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (capi.hip: PinnedBuf explains why)
+    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
+    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
+    p->pinned_cap = total;
+  }
+  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
+  const bool same = r_src == r_trg && bytes[0] == bytes[1];
+  Carver cut(p->pinned);
+  char* back = nullptr;
+  for (int i = 0; i < 5; i++) {
+    char* q = cut.take<char>(bytes[i]);
+    if (i == 3) { back = q; continue; }
+    if (!bytes[i] || (i == 1 && same)) continue;
+    std::memcpy(q, src[i], bytes[i]);
+    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
+  }
+  LISTS_TRY(hipMemsetAsync(p->dbuf[3], 0, bytes[3], p->st));
+  const int rc = sctl_amd_lists_eval_transpose_device(p, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[4], p->dbuf[3], digits, ctx, ctx_bytes, p->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[3], bytes[3], hipMemcpyDeviceToHost, p->st));
+  LISTS_TRY(hipStreamSynchronize(p->st));
+  const int64_t n = p->Ns * k.k0;      // g_src += device result
+  if (p->real == SCTL_AMD_F64) { double* o = (double*)g_src; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  else { float* o = (float*)g_src; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  return SCTL_AMD_OK;
+}
+
+// one-shot form: plan the transposed side only, evaluate, release
+int sctl_amd_eval_lists_transpose_host(int kernel, int real, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                       const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                       const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, int device) {
+  sctl_amd_lists* p = nullptr;
+  int rc = sctl_amd_lists_create_directions(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, SCTL_AMD_LISTS_TRANSPOSE, &p);
+  if (rc != SCTL_AMD_OK) return rc;
+  rc = sctl_amd_lists_eval_transpose_host(p, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes);
+  sctl_amd_lists_destroy(p);
+  return rc;
+}
+
 // ---- several densities over the lists (sctl_amd_lists_eval_densities_*, lists_multi_kernel.hpp) ----------------------------------------
 // The plan is the single-density plan: the same handle serves any nd.
 }  // extern "C"
@@ -321,6 +492,7 @@ template <class R> int lmulti_form(const ListsMultiEntry* me, int mode, int left
 int check_lists_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
   if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
   const KernelEntry& k = *p->k;
   if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
     return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
@@ -333,6 +505,7 @@ template <class R>
 int lists_eval_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits, const void* ctx, int ctx_bytes,
                            hipStream_t st) {
   const KernelEntry& k = *p->k;
+  const ListsSide& fw = p->side[0];
   const int64_t f_stride = p->Ns * k.k0, v_stride = p->Nt * k.k1;
   const ListsMultiEntry* me = lmulti_entry(k.id);
   const int mode = mode_for(p->real, digits);
@@ -347,13 +520,13 @@ int lists_eval_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, 
     const int M = kListMultiM[form], nact = nd - m0 < M ? nd - m0 : M;
     (void)hipGetLastError();
     ListMultiArgs<R> a{};
-    a.l = ListArgs<R>{{0}, (const ListItem*)p->d_items, (const ListRange*)p->d_ranges, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride,
-                      (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)p->d_groups, (const uint32_t*)p->d_flat};
-    std::memcpy(a.l.xcd_first, p->xcd_first, sizeof a.l.xcd_first);
+    a.l = ListArgs<R>{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride,
+                      (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
+    std::memcpy(a.l.xcd_first, fw.xcd_first, sizeof a.l.xcd_first);
     a.f_stride = f_stride; a.v_stride = v_stride; a.nact = nact;
-    lmulti_launch<R>(*me, mode, form)(a, p->nblocks, st);
+    lmulti_launch<R>(*me, mode, form)(a, fw.nblocks, st);
     LISTS_TRY(hipGetLastError());
-    count_work(p->pairs * nact, k);
+    count_work(fw.pairs * nact, k);
     m0 += nact;
   }
   return SCTL_AMD_OK;
@@ -368,7 +541,7 @@ int sctl_amd_lists_eval_densities_device(sctl_amd_lists* p, int nd, const void* 
   const int rc = check_lists_densities(p, nd, ctx, ctx_bytes);
   if (rc) return rc;
   if (nd == 1) return sctl_amd_lists_eval_device(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes, stream);
-  if (nd == 0 || p->nitems == 0) return SCTL_AMD_OK;
+  if (nd == 0 || p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device
   LISTS_TRY(scope.err);
@@ -386,7 +559,7 @@ int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_
   const int rc0 = check_lists_densities(p, nd, ctx, ctx_bytes);
   if (rc0) return rc0;
   if (nd == 1) return sctl_amd_lists_eval_host(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
-  if (nd == 0 || p->nitems == 0) return SCTL_AMD_OK;
+  if (nd == 0 || p->side[0].nitems == 0) return SCTL_AMD_OK;
   const KernelEntry& k = *p->k;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
@@ -453,7 +626,7 @@ int sctl_amd_eval_lists_device(int kernel, int real, int64_t nlists, const int64
   int rc = sctl_amd_lists_create(kernel, real, dev, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, &p);
   if (rc != SCTL_AMD_OK) return rc;
   rc = sctl_amd_lists_eval_device(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes, stream);
-  if (rc == SCTL_AMD_OK && p->nitems > 0 && hipStreamSynchronize((hipStream_t)stream) != hipSuccess)   // the work list is freed below
+  if (rc == SCTL_AMD_OK && p->side[0].nitems > 0 && hipStreamSynchronize((hipStream_t)stream) != hipSuccess)   // the work list is freed below
     rc = set_error(SCTL_AMD_ERR_HIP, "hipStreamSynchronize failed after the list evaluation");
   sctl_amd_lists_destroy(p);
   return rc;
