@@ -1,5 +1,5 @@
-// Host driver of the tile-centred Laplace single-layer path (centered_kernel.hpp): Morton-sort the targets on the device
-// (rocPRIM radix sort of 63-bit keys), evaluate on the sorted order, scatter-add the result back.  Everything is enqueued
+// Host driver of the tile-centred Laplace single-layer path (centered_kernel.hpp): sort the targets along the Hilbert curve on the device
+// (curve_key.hpp; rocPRIM radix sort of 63-bit keys), evaluate on the sorted order, scatter-add the result back.  Everything is enqueued
 // on the caller's stream; temporaries are carved out of the stream's scratch block (workspace.hpp).
 #include "centered_kernel.hpp"
 #include "centered_mfma_kernel.hpp"
@@ -95,7 +95,7 @@ template <class CP, class R, int MODE> void launch_centered(const EvalArgs<R>& a
 // v_trg[Nt] += scale * sum_s (kernel of the policy CP), mode = rsqrt refinement (ukernels.hpp)
 // Launch geometry of the centred kernel: one wave per workgroup, 64*T targets each.  The kernel holds 103 VGPRs, so 16
 // waves are resident per CU; the work per wave varies with its share of near sources (0.5 % .. 34 % at 2^20 uniform
-// points), so the source range is split until there are >= 64 "rounds" of workgroups (counted at 128 targets per wave) — measured on 2^20 x 2^20:
+// points in Z-curve order, when these rules were measured; at most 1.7 % in Hilbert order, round 6), so the source range is split until there are >= 64 "rounds" of workgroups (counted at 128 targets per wave) — measured on 2^20 x 2^20:
 // 1 split 517 ms, 4 splits 480 ms, 16 splits 469 ms (exact kernel on the same GPU: 520 ms).
 // Second rule (round 2): a split's source data (src_bytes per source: coordinates, density, normals as the kernel reads them) should fit the
 // 4 MB L2 of the XCD that owns the split (centered_kernel.hpp), i.e. <= 2 MB: at 2^23 fp32 sources in 2 splits every wave streamed 64 MB per
@@ -105,6 +105,8 @@ void centered_plan(int64_t Nt, int64_t Ns, int cus, int src_bytes, int out_bytes
   const int64_t wg_x = (Nt + kWaveBlock * 2 - 1) / (kWaveBlock * 2);
   const int64_t want = (int64_t)cus * 16 * 64;   // (x 32 until round 4: 2^20 x 2^20 in 32 instead of 16 splits — workgroups half as long, a shorter last round — 402.8 -> 398.5 ms,
                                                  //  at 10 digits 373.4 -> 369.7; 64 splits the same again: profiles/r04_ab_rank_splits.txt)
+                                                 // (round 6, targets in Hilbert order, workgroups of near-equal length: 16 splits again measured 360.1 against 359.2 ms — 32 stay:
+                                                 //  profiles/r06_ab_hilbert_prepass.txt)
   const int64_t ntile = (Ns + kWaveTile - 1) / kWaveTile;
   int64_t s = (want + wg_x - 1) / wg_x;
   const int64_t s_l2 = (Ns * src_bytes + (2 << 20) - 1) / (2 << 20);
@@ -194,7 +196,7 @@ hipError_t eval_centered_t(int64_t Nt, int64_t Ns, const R* xt, const R* xs, con
   hipLaunchKernelGGL((scatter_add_kernel<R>), dim3(nb), dim3(kBlock), 0, st, (const R*)outs, perm, Nt, K1, v_trg);
   return hipGetLastError();
 }
-// Morton order of n points that are ALREADY on the current device: bbox -> 63-bit keys -> rocPRIM radix sort (stable: ties keep the caller's
+// Curve order (Hilbert keys; the name is from the Z-curve of rounds 1-5) of n points that are ALREADY on the current device: bbox -> 63-bit keys -> rocPRIM radix sort (stable: ties keep the caller's
 // order) -> gather.  d_perm[i] = caller's index of the i-th point of the order, d_sorted = the coordinates in that order.  Temporaries come
 // from the stream's scratch block; everything is enqueued on st.  The operator handle (capi.hip: sctl_amd_op_set_targets) uses this instead of
 // a host sort: 2^20 points in ~1.5 ms against ~70 ms for std::sort on one host core.

@@ -14,10 +14,11 @@
 //
 // The far/near decision is per (wave, source) — uniform across the wave — and is made when a tile of 64 sources is staged
 // into LDS: far and near sources are compacted into two record lists, so both inner loops have uniform trip counts and
-// no per-pair branch.  The host side (centered.hip) Morton-sorts the targets first so that the 128 targets of a wave are
-// compact; results are scattered back through the permutation.
+// no per-pair branch.  The host side (centered.hip) sorts the targets along a space-filling curve first (Hilbert keys, curve_key.hpp; the Z-curve
+// until round 5, whence "morton" in the names) so that the targets of a wave are compact; results are scattered back through the permutation.
 #pragma once
 #include <sctl_amd/device/eval_kernel.hpp>
+#include "curve_key.hpp"
 
 namespace sctl_amd {
 
@@ -735,7 +736,7 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
   }
 }
 
-// ---- Morton ordering of the targets (host side drives these through rocPRIM's radix sort, capi.hip) ---------
+// ---- curve ordering of the targets (host side drives these through rocPRIM's radix sort, centered.hip) ---------
 // per-block bounding boxes -> bbox[block][6]
 template <class R> __global__ void __launch_bounds__(kBlock) bbox_partial_kernel(const R* x, int64_t n, double* part) {
   __shared__ double red[4 * 6];
@@ -764,17 +765,8 @@ template <class R> __global__ void __launch_bounds__(kBlock) bbox_partial_kernel
   }
 }
 
-__device__ __forceinline__ uint64_t spread21(uint64_t v) {   // 21 bits -> every third bit
-  v &= 0x1fffffull;
-  v = (v | (v << 32)) & 0x1f00000000ffffull;
-  v = (v | (v << 16)) & 0x1f0000ff0000ffull;
-  v = (v | (v << 8)) & 0x100f00f00f00f00full;
-  v = (v | (v << 4)) & 0x10c30c30c30c30c3ull;
-  v = (v | (v << 2)) & 0x1249249249249249ull;
-  return v;
-}
-
-// final bbox from the per-block ones (read by every thread: nblk is small), then 63-bit Morton keys + identity index
+// final bbox from the per-block ones (read by every thread: nblk is small), then the 63-bit curve keys (curve_key.hpp: the Hilbert index of the point's cell;
+// the Z-curve's bit interleave until round 5, hence the names) + identity index
 template <class R> __global__ void __launch_bounds__(kBlock) morton_keys_kernel(const R* x, int64_t n, const double* part, int nblk, uint64_t* keys, uint32_t* idx) {
   __shared__ double box[6];
   if (threadIdx.x < 6) {
@@ -786,15 +778,8 @@ template <class R> __global__ void __launch_bounds__(kBlock) morton_keys_kernel(
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  uint64_t key = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double w = box[3 + k] - box[k];
-    const double q = (w > 0) ? ((double)x[i * 3 + k] - box[k]) / w * 2097151.0 : 0.0;
-    const uint64_t qi = (q > 0) ? (uint64_t)((q < 2097151.0) ? q : 2097151.0) : 0ull;   // NaN -> 0
-    key |= spread21(qi) << k;
-  }
-  keys[i] = key;
+  const double p[3] = {(double)x[i * 3], (double)x[i * 3 + 1], (double)x[i * 3 + 2]};
+  keys[i] = curve_key(p, box);
   idx[i] = (uint32_t)i;
 }
 
