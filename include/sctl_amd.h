@@ -348,6 +348,32 @@ int sctl_amd_near_apply_densities_device(sctl_amd_near* op, int nd, const void* 
 int sctl_amd_op_eval_potential_densities(sctl_amd_op* op, int nd, const void* v_src_far, const void* f_near, void* v_trg, int accumulate,
                                          int digits, const void* ctx, int ctx_bytes);
 
+/* ---- the adjoint of the near field and of ComputePotential --------------------------------------------------------------------- */
+/* G += N^T W for the near-field operator N of sctl_amd_near_apply_* (U += N F): W[Ntrg*trg_dim] is gathered into near-list order
+ * (Wn[near_scatter_index[p]*trg_dim + k] = W[i*trg_dim + k] for the entries p of target i, the inverse of the per-target
+ * accumulation) and every element's block is applied transposed, G[f_off_e + s] += sum_t K_e[s][t] Wn[u_off_e + t]; G has
+ * density_len values and is ACCUMULATED into.  Every entry of K_near is read once per application; the sums go across the lanes of a
+ * wave by a fixed tree (no atomics), so results are bit-identical from run to run.  Elements without a matrix (K_near_cnt[e] == 0) or
+ * without near targets add nothing: their entries of G keep their bits.  What the transposed direction needs beyond the forward's
+ * device arrays (its work list, the gathered W) is allocated on the first transposed call, not by sctl_amd_near_create.  That first call
+ * therefore allocates and copies the work list synchronously before it enqueues (it cannot be captured into a graph); later calls only enqueue.  Null handle
+ * or arrays: SCTL_AMD_ERR_BAD_ARGUMENT before any device work; an operator without entries returns SCTL_AMD_OK and touches nothing.
+ * Several weight vectors per call are NOT provided in the transposed direction: call once per vector. */
+int sctl_amd_near_apply_transpose_host(sctl_amd_near* op, const void* W, void* G);                   /* HOST arrays, G accumulated into            */
+int sctl_amd_near_apply_transpose_device(sctl_amd_near* op, const void* W, void* G, void* stream);   /* DEVICE arrays, enqueue, G accumulated into */
+/* The adjoint of sctl_amd_op_eval (g_src = D_w A^T C_n^T w) and of sctl_amd_op_eval_potential (that, and g_near = N^T w) on the
+ * operator's devices: A the far-field kernel sum, D_w the source weights and C_n the contraction with the target normals where they
+ * are set, N the attached near field.  HOST arrays: w_trg[Nt*TrgDim] (Nt*TrgDim/3 with target normals), g_src / g_src_far[Ns*SrcDim],
+ * g_near[sum(elem_nds_cnt)*SrcDim].  Every device takes its target slab of w (in the operator's own target order), expands it with the
+ * normals, runs the transposed kernel sum of the slab against all sources, scales by the weights and applies its near sub-operator
+ * transposed on the same stream; the host adds the devices' partial results in device order, so results agree between device lists to
+ * rounding, not bit for bit.  accumulate != 0 adds to the output arrays, else they are overwritten.  Errors as
+ * sctl_amd_op_eval_potential; a registered kernel whose functor supplies no pair_t gives SCTL_AMD_ERR_UNKNOWN_KERNEL.  The counters
+ * grow by Nt*Ns.  There are no rank-parallel (_dist) forms of these entries. */
+int sctl_amd_op_eval_transpose(sctl_amd_op* op, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes);
+int sctl_amd_op_eval_potential_transpose(sctl_amd_op* op, const void* w_trg, void* g_src_far, void* g_near, int accumulate, int digits,
+                                         const void* ctx, int ctx_bytes);
+
 int sctl_amd_near_info(const sctl_amd_near* op, int64_t* density_len, int64_t* potential_len, int64_t* near_entries,
                        int64_t* operator_bytes, int64_t* workgroups);
 void sctl_amd_near_destroy(sctl_amd_near* op);

@@ -9,7 +9,8 @@
 //
 // Same names and argument meaning as the reference for everything on that leg: ElementListBase (Size, GetNodeCoord,
 // GetFarFieldNodes, GetFarFieldDensity, MatrixFree), BoundaryIntegralOp (SetAccuracy, AddElemList, GetElemList,
-// DeleteElemList, SetTargetCoord, SetTargetNormal, Dim, Setup, ClearSetup, ComputeFarField, ComputePotential).
+// DeleteElemList, SetTargetCoord, SetTargetNormal, Dim, Setup, ClearSetup, ComputeFarField, ComputePotential), and their adjoints
+// ComputeFarFieldTranspose, ComputeNearInteracTranspose, ComputePotentialTranspose.
 //
 // NEAR FIELD.  For element lists with a near zone (far-field distance > 0) the reference corrects
 // the far-field quadrature near each element with precomputed operator matrices:
@@ -297,7 +298,98 @@ template <class Real, class Kernel> class BoundaryIntegralOp {
     AddMatrixFreeNearFieldRows(U, F);
   }
 
+  // ---- the adjoint (BiCG / QMR / LSQR, adjoint solves, norm estimates): G of size Dim(0), W of size Dim(1), <W, ComputeX(F)> = <ComputeXTranspose(W), F>.
+  // The far part runs on the far-field operator's devices (sctl_amd_op_eval_transpose: target normals, transposed kernel sum, weights) and is
+  // mapped back from the far-field nodes to the element nodes by each list's FarFieldDensityOperatorTranspose; the near part is
+  // sctl_amd_near_apply_transpose_host, or both in one pass over the devices (sctl_amd_op_eval_potential_transpose).  A matrix-free element
+  // list has no adjoint of its EvalNearInterac: the near and the whole transposed potential of such an operator abort. ----
+  void ComputeFarFieldTranspose(Vector<Real>& G, const Vector<Real>& W) const {
+    SetupBasic();
+    SetupFar();
+    const Long Nsrc = X_far.Dim() / COORD_DIM, Ntrg = Xtrg.Dim() / COORD_DIM;
+    SCTL_AMD_ASSERT(W.Dim() == Dim(1));
+    if (G.Dim() != Dim(0)) G.ReInit(Dim(0));
+    G.SetZero();
+    if (!Ntrg || !Nsrc) return;
+    Vector<Real> G_far(Nsrc * KDIM0);
+    CheckStatus(sctl_amd_op_eval_transpose(far_op, W.begin(), G_far.begin(), /*accumulate*/ 0, fmm_digits(), ker_.GetCtxPtr(), (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_transpose");
+    ScatterFarFieldGradient(G, G_far);
+  }
+
+  // G is ACCUMULATED into when it has the right size, as ComputeNearInterac does with U
+  void ComputeNearInteracTranspose(Vector<Real>& G, const Vector<Real>& W) const {
+    RefuseMatrixFree("ComputeNearInteracTranspose");
+    Setup();
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long Ntrg = Xtrg.Dim() / COORD_DIM, Nelem = near_elem_cnt.Dim();
+    SCTL_AMD_ASSERT(W.Dim() == Dim(1));
+    if (G.Dim() != Dim(0)) {
+      G.ReInit(Dim(0));
+      G.SetZero();
+    }
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near) return;
+    if (!near_op) {
+      const int rc = sctl_amd_near_create(RealTag<Real>::value, DeviceSet::Get()[0], Nelem, (int)KDIM0, (int)KDIM1_, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt),
+                                          PtrOf(K_near_cnt), K_near.Dim() ? (const void*)K_near.begin() : nullptr, Ntrg, PtrOf(near_scatter_index),
+                                          PtrOf(near_trg_cnt), PtrOf(near_trg_dsp), &near_op);
+      CheckStatus(rc, "sctl_amd_near_create");
+    }
+    CheckStatus(sctl_amd_near_apply_transpose_host(near_op, W.begin(), G.begin()), "sctl_amd_near_apply_transpose_host");
+  }
+
+  void ComputePotentialTranspose(Vector<Real>& G, const Vector<Real>& W) const {
+    RefuseMatrixFree("ComputePotentialTranspose");
+    Setup();
+    const Long Nelem = near_elem_cnt.Dim();
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near || !far_op) {   // as ComputePotential: the two legs as they are
+      ComputeFarFieldTranspose(G, W);
+      ComputeNearInteracTranspose(G, W);
+      return;
+    }
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long Nsrc = X_far.Dim() / COORD_DIM;
+    SCTL_AMD_ASSERT(W.Dim() == Dim(1));
+    if (G.Dim() != Dim(0)) G.ReInit(Dim(0));
+    if (!near_attached) {
+      CheckStatus(sctl_amd_op_set_near(far_op, (int)KDIM0, (int)KDIM1_, Nelem, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt), PtrOf(K_near_cnt),
+                                       K_near.Dim() ? (const void*)K_near.begin() : nullptr, PtrOf(near_scatter_index), PtrOf(near_trg_cnt), PtrOf(near_trg_dsp)),
+                  "sctl_amd_op_set_near");
+      near_attached = true;
+    }
+    Vector<Real> G_far(Nsrc * KDIM0);
+    CheckStatus(sctl_amd_op_eval_potential_transpose(far_op, W.begin(), G_far.begin(), G.begin(), /*accumulate*/ 0, fmm_digits(), ker_.GetCtxPtr(),
+                                                     (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_potential_transpose");
+    ScatterFarFieldGradient(G, G_far);
+  }
+
  private:
+  void RefuseMatrixFree(const char* what) const {
+    for (const auto& it : elem_lst_map)
+      if (it.second->MatrixFree())
+        SCTL_AMD_ERROR((std::string(what) + ": the operator holds a matrix-free element list, and there is no adjoint of its EvalNearInterac").c_str());
+  }
+
+  // G += (GetFarFieldDensity operator)^T G_far, one element at a time: the adjoint of GatherFarFieldDensity
+  void ScatterFarFieldGradient(Vector<Real>& G, Vector<Real>& G_far) const {
+    for (size_t lst = 0; lst < elem_lst_name.size(); lst++) {
+      const ElementListBase<Real>* elem_lst = elem_lst_map.at(elem_lst_name[lst]);
+      for (Long j = 0; j < elem_lst_cnt[(Long)lst]; j++) {
+        const Long e = elem_lst_dsp[(Long)lst] + j, ns = elem_nds_cnt_far[e], N0 = elem_nds_cnt[e] * KDIM0;
+        if (!ns || !N0) continue;
+        const Matrix<Real> Min(ns * KDIM0, 1, G_far.begin() + elem_nds_dsp_far[e] * KDIM0, false);
+        Matrix<Real> Mout;
+        elem_lst->FarFieldDensityOperatorTranspose(Mout, Min, j);
+        const Matrix<Real>& D = (Mout.Dim(0) && Mout.Dim(1)) ? Mout : Min;
+        SCTL_AMD_ASSERT(D.Dim(0) == N0 && D.Dim(1) == 1);
+        for (Long l = 0; l < N0; l++) G[elem_nds_dsp[e] * KDIM0 + l] += D[l][0];
+      }
+    }
+  }
+
   // GatherFarFieldDensity, one row at a time, into F_far_all (nd x far-field density length)
   void GatherFarFieldDensities(Matrix<Real>& F_far_all, const Matrix<Real>& F) const {
     const Long nd = F.Dim(0), n_far = (X_far.Dim() / COORD_DIM) * KDIM0;

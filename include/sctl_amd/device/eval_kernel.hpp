@@ -334,4 +334,12 @@ template <class R> __global__ void __launch_bounds__(kBlock) normal_dot_kernel(c
   u[i] = v[i * 3] * nrm[t * 3] + v[i * 3 + 1] * nrm[t * 3 + 1] + v[i * 3 + 2] * nrm[t * 3 + 2];
 }
 
+// the adjoint of normal_dot_kernel: wf[t][k*3+l] = w[t][k] * nrm[t][l]
+template <class R> __global__ void __launch_bounds__(kBlock) normal_expand_kernel(const R* w, const R* nrm, R* wf, int64_t nt, int k1r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nt * k1r * 3) return;
+  const int64_t j = i / 3, t = j / k1r;
+  wf[i] = w[j] * nrm[t * 3 + (i - j * 3)];
+}
+
 }  // namespace sctl_amd

@@ -34,7 +34,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan",
            "sctl_amd_lists_create_directions", "sctl_amd_lists_eval_transpose_device", "sctl_amd_lists_eval_transpose_host", "sctl_amd_lists_transpose_info",
            "sctl_amd_eval_lists_transpose_host",
-           "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan"]
+           "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan",
+           "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose"]
 
 
 class SctlAmdError(RuntimeError):
@@ -144,6 +145,10 @@ def lib():
     L.sctl_amd_eval_grad_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_grad_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_grad_plan.argtypes = [ci, ci, i64, i64, ci] + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)] * 2
+    L.sctl_amd_near_apply_transpose_host.argtypes = [vp, vp, vp]
+    L.sctl_amd_near_apply_transpose_device.argtypes = [vp, vp, vp, vp]
+    L.sctl_amd_op_eval_transpose.argtypes = [vp, vp, vp, ci, ci, vp, ci]
+    L.sctl_amd_op_eval_potential_transpose.argtypes = [vp, vp, vp, vp, ci, ci, vp, ci]
     _LIB = L
     return L
 
@@ -683,6 +688,41 @@ class DirectOp:
                "op_eval_potential_densities")
         return V_trg
 
+    def _out(self, a, n, what):
+        if a is None:
+            return np.zeros(n, dtype=self.dtype)
+        if not isinstance(a, np.ndarray) or a.size != n or a.dtype != self.dtype or not a.flags.c_contiguous:
+            raise SctlAmdError("%s must be a contiguous %s array of %d values" % (what, self.dtype, n))
+        return a
+
+    def eval_transpose(self, w_trg, g_src=None, accumulate=False, digits=-1):
+        """The adjoint of eval() (sctl_amd_op_eval_transpose): g_src = D_w A^T C_n^T w_trg, with the source weights and target normals
+        that are set; w_trg holds Nt*TrgDim values (Nt*TrgDim/3 with target normals), g_src Ns*SrcDim."""
+        k1 = self.info["k1"] // 3 if getattr(self, "_dot", False) else self.info["k1"]
+        if np.size(w_trg) != self.Nt * k1:
+            raise SctlAmdError("w_trg must hold %d values" % (self.Nt * k1))
+        g_src = self._out(g_src, self.Ns * self.info["k0"], "g_src")
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_transpose(self._h, _np_ptr(w_trg, self.dtype, self.Nt * k1, "w_trg"), _np_ptr(g_src, self.dtype, g_src.size, "g_src"),
+                                                1 if accumulate else 0, digits, cp, cb), "op_eval_transpose")
+        return g_src
+
+    def eval_potential_transpose(self, w_trg, g_src_far=None, g_near=None, accumulate=False, digits=-1):
+        """The adjoint of eval_potential() (sctl_amd_op_eval_potential_transpose): returns (g_src_far, g_near), the gradients with respect
+        to the far-field density (Ns*SrcDim values) and the near-field density (element nodes x SrcDim)."""
+        if not hasattr(self, "_near_k1"):
+            raise SctlAmdError("no near-field operator attached: call set_near first")
+        k1 = self._near_k1
+        if np.size(w_trg) != self.Nt * k1:
+            raise SctlAmdError("w_trg must hold %d values" % (self.Nt * k1))
+        g_src_far = self._out(g_src_far, self.Ns * self.info["k0"], "g_src_far")
+        g_near = self._out(g_near, self._near_len, "g_near")
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_potential_transpose(self._h, _np_ptr(w_trg, self.dtype, self.Nt * k1, "w_trg"),
+                                                          _np_ptr(g_src_far, self.dtype, g_src_far.size, "g_src_far"), _np_ptr(g_near, self.dtype, g_near.size, "g_near"),
+                                                          1 if accumulate else 0, digits, cp, cb), "op_eval_potential_transpose")
+        return g_src_far, g_near
+
     def close(self):
         if self._h:
             lib().sctl_amd_op_destroy(self._h)
@@ -737,6 +777,31 @@ class NearOp:
             _check(lib().sctl_amd_near_apply_device(self._h, _t_ptr(F, tdt, self.density_len, "F"), _t_ptr(U, tdt, self.potential_len, "U"),
                                                     C.c_void_p(st.cuda_stream)), "near_apply_device")
         return U
+
+    def apply_transpose(self, W, G=None):
+        """G += N^T W (numpy arrays, sctl_amd_near_apply_transpose_host): W of potential_len values, G of density_len; G=None starts from zero."""
+        W = np.ascontiguousarray(W, dtype=self.dtype)
+        if W.size != self.potential_len:
+            raise SctlAmdError("weights must hold %d values" % self.potential_len)
+        if G is None:
+            G = np.zeros(self.density_len, dtype=self.dtype)
+        if G.size != self.density_len or G.dtype != self.dtype or not G.flags.c_contiguous:
+            raise SctlAmdError("density gradient must be a contiguous %s array of %d values" % (self.dtype, self.density_len))
+        p = lambda a: None if a.size == 0 else a.ctypes.data_as(C.c_void_p)
+        _check(lib().sctl_amd_near_apply_transpose_host(self._h, p(W), p(G)), "near_apply_transpose_host")
+        return G
+
+    def apply_transpose_device(self, W, G, stream=None):
+        """The same on torch CUDA tensors, enqueued on `stream` (default: torch's current stream); G is accumulated into."""
+        import torch
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if W.numel() != self.potential_len or G.numel() != self.density_len:
+            raise SctlAmdError("weights and density gradient must hold %d and %d values" % (self.potential_len, self.density_len))
+        with torch.cuda.device(W.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_near_apply_transpose_device(self._h, _t_ptr(W, tdt, self.potential_len, "W"), _t_ptr(G, tdt, self.density_len, "G"),
+                                                              C.c_void_p(st.cuda_stream)), "near_apply_transpose_device")
+        return G
 
     def apply_densities(self, F, U=None):
         """apply() for nd densities with the operator read once per pass (sctl_amd_near_apply_densities_host): F of shape

@@ -16,7 +16,14 @@ plan.eval_transpose_device; densities only.
 
     plan = sctl_amd.ListsPlan("Stokes3D-FxU", np.float64, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, directions="both")
     u = sctl_amd.autograd.lists_sum(plan, r_trg, r_src, None, v_src)
-    u.square().sum().backward()                                                      # v_src.grad = sum over the lists of A_l^T (2 u)"""
+    u.square().sum().backward()                                                      # v_src.grad = sum over the lists of A_l^T (2 u)
+
+near_apply is NearOp.apply_device (the near-zone correction of a BoundaryIntegralOp, u = N f) with backward NearOp.apply_transpose_device;
+potential is DirectOp.eval_potential (ComputePotential: far field, weights, target normals and the attached near field; host tensors) with
+backward DirectOp.eval_potential_transpose.  Both differentiate the densities only.
+
+    u = sctl_amd.autograd.near_apply(near_op, f)                                     # torch CUDA tensor f of near_op.density_len values
+    u = sctl_amd.autograd.potential(direct_op, f_far, f_near)                        # torch CPU tensors"""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -111,3 +118,46 @@ def lists_sum(plan, r_trg, r_src, n_src, v_src, digits=-1):
         if t is not None and t.requires_grad:
             raise api.SctlAmdError("lists_sum differentiates with respect to the densities only: %s requires grad" % what)
     return _ListsSum.apply(plan, r_trg, r_src, n_src, v_src, digits)
+
+
+class _NearApply(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, op, F):
+        fn_ctx.op = op
+        return op.apply_device(F.detach().contiguous(), torch.zeros(op.potential_len, dtype=F.dtype, device=F.device))
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_u):
+        op = fn_ctx.op
+        return None, op.apply_transpose_device(grad_u.contiguous(), torch.zeros(op.density_len, dtype=grad_u.dtype, device=grad_u.device))
+
+
+def near_apply(op, F):
+    """NearOp.apply_device from zero on a torch CUDA tensor (a fresh result, potential_len values) that autograd can differentiate with
+    respect to the density F: the backward is NearOp.apply_transpose_device on the forward's stream, and is once-differentiable."""
+    return _NearApply.apply(op, F)
+
+
+class _Potential(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, op, f_far, f_near, digits):
+        fn_ctx.op, fn_ctx.digits = op, digits
+        u = op.eval_potential(f_far.detach().contiguous().numpy(), f_near.detach().contiguous().numpy(), digits=digits)
+        return torch.from_numpy(u)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_u):
+        g_far, g_near = fn_ctx.op.eval_potential_transpose(grad_u.contiguous().numpy(), digits=fn_ctx.digits)
+        need = fn_ctx.needs_input_grad
+        return None, torch.from_numpy(g_far) if need[1] else None, torch.from_numpy(g_near) if need[2] else None, None
+
+
+def potential(op, f_far, f_near, digits=-1):
+    """DirectOp.eval_potential on torch HOST tensors (the operator handle moves densities and potential itself) that autograd can differentiate
+    with respect to the far-field and the near-field density: the backward is DirectOp.eval_potential_transpose at the same digits."""
+    for what, t in (("f_far", f_far), ("f_near", f_near)):
+        if t.is_cuda:
+            raise api.SctlAmdError("potential takes host tensors: %s is a CUDA tensor" % what)
+    return _Potential.apply(op, f_far, f_near, digits)

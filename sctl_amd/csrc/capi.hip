@@ -1466,6 +1466,104 @@ int sctl_amd_op_eval_potential(sctl_amd_op* op, const void* v_src_far, const voi
   return op_eval_impl(op, v_src_far, (op && op->near_f_len == 0) ? (const void*)&nothing : f_near, v_trg, accumulate, digits, ctx, ctx_bytes);
 }
 
+// The adjoint of op_eval_impl for one weight vector: g_far = D_w A^T C_n^T w and, with_near, g_near = N^T w.  Every device works on its
+// target slab; the partial results wait in the devices' staging buffers and are added on the host in device order.
+static int op_eval_transpose_impl(sctl_amd_op* op, const void* w_trg, void* g_far, void* g_near, bool with_near, int accumulate, int digits, const void* ctx,
+                                  int ctx_bytes) {
+  if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  const KernelEntry& k = *op->k;
+  if (with_near && op->near.empty()) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "no near-field operator attached: call sctl_amd_op_set_near first");
+  if (with_near && op->near_trg_dim != (op->have_trg_normals ? k.k1 / 3 : k.k1))
+    return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "the attached near-field operator has another potential dimension than the far field delivers");
+  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
+    return fail(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if ((op->Nt > 0 && !w_trg) || (op->Ns > 0 && !g_far) || (with_near && op->near_f_len > 0 && !g_near))
+    return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or density-gradient array");
+  if (!has_transpose(k)) return no_transpose(k);
+  const size_t rs = (op->real == SCTL_AMD_F64) ? 8 : 4;
+  const int64_t Ns = op->Ns;
+  const int k1w = op->have_trg_normals ? k.k1 / 3 : k.k1;   // components of w per target
+  const size_t fbytes = (size_t)Ns * k.k0 * rs, nbytes = with_near ? (size_t)op->near_f_len * rs : 0, wrow = (size_t)k1w * rs;
+  std::vector<char> sorted;   // w in the operator's own (Morton) target order
+  if (!op->perm.empty()) {
+    sorted.resize((size_t)op->Nt * wrow);
+    for (int64_t i = 0; i < op->Nt; i++) std::memcpy(&sorted[(size_t)i * wrow], (const char*)w_trg + (size_t)op->perm[(size_t)i] * wrow, wrow);
+  }
+  const char* wsrc = sorted.empty() ? (const char*)w_trg : sorted.data();
+  std::vector<const char*> part_far(op->devs.size(), nullptr), part_near(op->devs.size(), nullptr);
+  const int rc_all = op_for_each_device(op, [&](OpDevice& d) -> int {
+    const int64_t nt = d.t1 - d.t0;
+    if (nt == 0) return SCTL_AMD_OK;
+    const size_t g = (size_t)(&d - op->devs.data());
+    const size_t wbytes = (size_t)nt * wrow;
+    DeviceScope dev_scope(d.device);
+    HIP_TRY(dev_scope.err);
+    HIP_TRY(grow(&d.f, &d.cap_f, fbytes));
+    HIP_TRY(grow(&d.v, &d.cap_v, (size_t)nt * k.k1 * rs));
+    if (op->have_trg_normals) HIP_TRY(grow(&d.u, &d.cap_u, wbytes));
+    HIP_TRY(d.stage.reserve(pad256(wbytes) + pad256(fbytes) + pad256(nbytes)));
+    void* w_dev = op->have_trg_normals ? d.u : d.v;   // the slab of w as the caller gave it: what the near field takes
+    HIP_TRY(upload(w_dev, wsrc + (size_t)d.t0 * wrow, wbytes, d.stage, d.st));
+    if (op->have_trg_normals) {   // w_full[t][k*3+l] = w[t][k] n_trg[t][l]: the adjoint of the contraction with the target normal
+      const unsigned nb = (unsigned)((nt * k.k1 + kBlock - 1) / kBlock);
+      if (op->real == SCTL_AMD_F64) hipLaunchKernelGGL((normal_expand_kernel<double>), dim3(nb), dim3(kBlock), 0, d.st, (const double*)d.u, (const double*)d.nt, (double*)d.v, nt, k1w);
+      else hipLaunchKernelGGL((normal_expand_kernel<float>), dim3(nb), dim3(kBlock), 0, d.st, (const float*)d.u, (const float*)d.nt, (float*)d.v, nt, k1w);
+      HIP_TRY(hipGetLastError());
+    }
+    if (fbytes) HIP_TRY(hipMemsetAsync(d.f, 0, fbytes, d.st));
+    int rc = SCTL_AMD_OK;
+    if (Ns == 0) {}
+    else if (op->real == SCTL_AMD_F64)
+      rc = eval_transpose_device_t<double>(k, op->real, nt, Ns, (const double*)d.xt, (const double*)d.xs, (const double*)d.xn, (const double*)d.v, (double*)d.f, digits, ctx, d.st);
+    else
+      rc = eval_transpose_device_t<float>(k, op->real, nt, Ns, (const float*)d.xt, (const float*)d.xs, (const float*)d.xn, (const float*)d.v, (float*)d.f, digits, ctx, d.st);
+    if (rc) return rc;
+    if (op->have_weights && Ns > 0) {   // the adjoint of density x quadrature weights is the same scaling
+      const unsigned nb = (unsigned)((Ns * k.k0 + kBlock - 1) / kBlock);
+      if (op->real == SCTL_AMD_F64) hipLaunchKernelGGL((scale_density_kernel<double>), dim3(nb), dim3(kBlock), 0, d.st, (double*)d.f, (const double*)d.w, Ns, k.k0);
+      else hipLaunchKernelGGL((scale_density_kernel<float>), dim3(nb), dim3(kBlock), 0, d.st, (float*)d.f, (const float*)d.w, Ns, k.k0);
+      HIP_TRY(hipGetLastError());
+    }
+    const bool near_here = nbytes && op->near[g];
+    if (near_here) {
+      HIP_TRY(hipMemsetAsync(op->near_f[g], 0, nbytes, d.st));
+      rc = sctl_amd_near_apply_transpose_device(op->near[g], w_dev, op->near_f[g], d.st);
+      if (rc) return rc;
+    }
+    char* out_f = d.stage.take(fbytes);
+    if (fbytes) HIP_TRY(hipMemcpyAsync(out_f, d.f, fbytes, hipMemcpyDeviceToHost, d.st));
+    char* out_n = d.stage.take(nbytes);
+    if (near_here) HIP_TRY(hipMemcpyAsync(out_n, op->near_f[g], nbytes, hipMemcpyDeviceToHost, d.st));
+    HIP_TRY(hipStreamSynchronize(d.st));
+    part_far[g] = out_f;
+    if (near_here) part_near[g] = out_n;
+    return SCTL_AMD_OK;
+  });
+  if (rc_all) return rc_all;
+  auto combine = [&](void* out, const std::vector<const char*>& parts, size_t bytes) {   // device order: a fixed order
+    if (!bytes) return;
+    if (!accumulate) std::memset(out, 0, bytes);
+    const int64_t n = (int64_t)(bytes / rs);
+    for (const char* p : parts) {
+      if (!p) continue;
+      if (op->real == SCTL_AMD_F64) { double* o = (double*)out; const double* s = (const double*)p; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+      else { float* o = (float*)out; const float* s = (const float*)p; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+    }
+  };
+  combine(g_far, part_far, fbytes);
+  if (with_near) combine(g_near, part_near, nbytes);
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_op_eval_transpose(sctl_amd_op* op, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes) {
+  return op_eval_transpose_impl(op, w_trg, g_src, nullptr, false, accumulate, digits, ctx, ctx_bytes);
+}
+
+int sctl_amd_op_eval_potential_transpose(sctl_amd_op* op, const void* w_trg, void* g_src_far, void* g_near, int accumulate, int digits, const void* ctx,
+                                         int ctx_bytes) {
+  return op_eval_transpose_impl(op, w_trg, g_src_far, g_near, true, accumulate, digits, ctx, ctx_bytes);
+}
+
 static void op_release_near(sctl_amd_op* op) {
   RestoreDevice restore;
   for (size_t g = 0; g < op->near.size(); g++) {

@@ -214,6 +214,136 @@ __global__ void __launch_bounds__(256) near_accumulate_multi_kernel(int64_t ntrg
     if (m < nact) U[(int64_t)m * u_stride + idx] = acc[m];
 }
 
+// ---- transposed application (sctl_amd_near_apply_transpose_*): G[f_off + s] += sum_t K[k_off + s * trg_dof + t] * Wn[u_off + t] -----------------
+// A row of a block is contiguous, so lanes run along t and the sum goes ACROSS lanes.  One wave holds 8 loads per lane in flight: 8 / NC
+// row steps times NC column chunks.  A row step is 64 / W rows, W = 2^lw lanes per row: W = 64 for blocks at least 64 columns wide, a
+// narrower block packs several rows into the wave and the reduction stops at width W.  Each row's partial sums are added in a lane in
+// the order of the column passes, then across the W lanes by an xor butterfly: a fixed tree, every lane of the row ends with the same bits.
+struct NearWorkT {     // rows [r0, r1) of one element's block
+  int64_t k_off, f_off, u_off;
+  int32_t src_dof, trg_dof, r0, r1;
+  int32_t lw;          // log2 of the lanes per row
+  int32_t nc;          // column chunks of a row in flight: 1, 2, 4 or 8 (blocks with few rows fill the 8 loads along the row instead)
+};
+
+constexpr int kSplitCols = 1024;   // rows at least this long are cut over the four waves of a workgroup
+
+// Wn[scatter[p] * k1 + k] = W[i * k1 + k] for the entries p of target i: the inverse of near_accumulate_kernel
+template <class R>
+__global__ void __launch_bounds__(256) near_gather_kernel(int64_t ntrg, int k1, const int64_t* __restrict__ scatter, const int64_t* __restrict__ trg_cnt,
+                                                          const int64_t* __restrict__ trg_dsp, const R* __restrict__ W, R* __restrict__ Wn) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ntrg * k1) return;
+  const int64_t i = idx / k1;
+  const int k = (int)(idx - i * k1);
+  const int64_t p0 = trg_dsp[i], p1 = p0 + trg_cnt[i];
+  if (p1 == p0) return;
+  const R w = W[idx];
+  for (int64_t p = p0; p < p1; p++) Wn[scatter[p] * k1 + k] = w;
+}
+
+// Rows rb + ru * (64 / W) + lane / W, ru = 0 .. 8 / NC - 1, against the columns [c0, c1): acc[ru] = the row's sum, in every lane of the row.
+// rb, r1, c0, c1 and lw are wave-uniform.  K_near is read exactly once per application, with non-temporal loads as in near_column_sum.
+template <class R, int NC>
+__device__ __forceinline__ void near_t_batch(const R* __restrict__ Kb, const R* __restrict__ We, int ld, int rb, int r1, int c0, int c1, int lw, int lane,
+                                             R (&acc)[8 / NC]) {
+  constexpr int NR = 8 / NC;
+  const int W = 1 << lw, step = 64 >> lw, row0 = rb + (lane >> lw), l = lane & (W - 1);
+#pragma unroll
+  for (int ru = 0; ru < NR; ru++) acc[ru] = 0;
+  const bool rows_full = rb + NR * step <= r1;
+  for (int cb = c0; cb < c1; cb += NC * W) {
+    R kv[8], wv[NC];
+    if (rows_full && cb + NC * W <= c1) {     // whole batch inside the block: no predicates
+#pragma unroll
+      for (int cu = 0; cu < NC; cu++) wv[cu] = We[cb + cu * W + l];
+#pragma unroll
+      for (int u = 0; u < 8; u++) kv[u] = __builtin_nontemporal_load(Kb + (int64_t)(row0 + (u / NC) * step) * ld + (cb + (u % NC) * W + l));
+    } else {
+#pragma unroll
+      for (int cu = 0; cu < NC; cu++) {
+        const int t = cb + cu * W + l;
+        wv[cu] = (t < c1) ? We[t] : R(0);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int r = row0 + (u / NC) * step, t = cb + (u % NC) * W + l;
+        kv[u] = (r < r1 && t < c1) ? __builtin_nontemporal_load(Kb + (int64_t)r * ld + t) : R(0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u++) acc[u / NC] += kv[u] * wv[u % NC];
+  }
+#pragma unroll
+  for (int ru = 0; ru < NR; ru++)
+    for (int o = W >> 1; o > 0; o >>= 1) acc[ru] += __shfl_xor(acc[ru], o);
+}
+
+// one wave, all rows of an item; lane 0 of a row adds the row's sum to its entry of G
+template <class R, int NC>
+__device__ __forceinline__ void near_t_item(const NearWorkT& w, const R* __restrict__ K, const R* __restrict__ Wn, R* __restrict__ G, int lane) {
+  constexpr int NR = 8 / NC;
+  const int step = 64 >> w.lw;
+  for (int rb = w.r0; rb < w.r1; rb += NR * step) {
+    R acc[NR];
+    near_t_batch<R, NC>(K + w.k_off, Wn + w.u_off, w.trg_dof, rb, w.r1, 0, w.trg_dof, w.lw, lane, acc);
+    const int row0 = rb + (lane >> w.lw);
+#pragma unroll
+    for (int ru = 0; ru < NR; ru++) {
+      const int r = row0 + ru * step;
+      if ((lane & ((1 << w.lw) - 1)) == 0 && r < w.r1) G[w.f_off + r] += acc[ru];
+    }
+  }
+}
+
+//   split items (rows of kSplitCols columns and more): one per workgroup, at most 8 rows (one or two rows where the block has fewer than 8,
+//          which then have their 8 loads along the row: 8 chunks of one row, or 4 chunks of two where a wave's run has fewer than 8 chunks); the four waves take four runs of whole 64-column chunks, their sums meet in LDS and wave 0 adds
+//          them in the order ((0 + 1) + (2 + 3));
+//   wave items : one per WAVE, as the narrow items of near_gemv_kernel.
+// No atomics: a row belongs to one item, its entry of G is written by one lane.
+template <class R>
+__global__ void __launch_bounds__(kNearBlock) near_gemv_t_kernel(const NearWorkT* __restrict__ split_work, int64_t n_split, const NearWorkT* __restrict__ wave_work,
+                                                                 int64_t n_wave, const R* __restrict__ K, const R* __restrict__ Wn, R* __restrict__ G) {
+  __shared__ R part[kRowGroups][8];
+  const int lane = threadIdx.x & (kCols - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kCols));
+  for (int64_t wi = blockIdx.x; wi < n_split; wi += gridDim.x) {
+    const NearWorkT w = split_work[wi];
+    const int per = ((w.trg_dof + kCols - 1) / kCols + kRowGroups - 1) / kRowGroups * kCols;   // columns per wave
+    const int c0 = wave * per < w.trg_dof ? wave * per : w.trg_dof, c1 = c0 + per < w.trg_dof ? c0 + per : w.trg_dof;
+    R acc[8];
+    if (w.nc == 8) {
+      R one[1];
+      near_t_batch<R, 8>(K + w.k_off, Wn + w.u_off, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, one);
+      acc[0] = one[0];
+#pragma unroll
+      for (int j = 1; j < 8; j++) acc[j] = 0;
+    } else if (w.nc == 4) {   // two rows, four chunks each
+      R two[2];
+      near_t_batch<R, 4>(K + w.k_off, Wn + w.u_off, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, two);
+      acc[0] = two[0];
+      acc[1] = two[1];
+#pragma unroll
+      for (int j = 2; j < 8; j++) acc[j] = 0;
+    } else {
+      near_t_batch<R, 1>(K + w.k_off, Wn + w.u_off, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, acc);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (lane == j) part[wave][j] = acc[j];
+    __syncthreads();
+    if (threadIdx.x < 8 && w.r0 + (int)threadIdx.x < w.r1)
+      G[w.f_off + w.r0 + threadIdx.x] += (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+    __syncthreads();
+  }
+  for (int64_t wi = (int64_t)blockIdx.x * kRowGroups + wave; wi < n_wave; wi += (int64_t)gridDim.x * kRowGroups) {
+    const NearWorkT w = wave_work[wi];
+    if (w.nc == 1) near_t_item<R, 1>(w, K, Wn, G, lane);
+    else if (w.nc == 2) near_t_item<R, 2>(w, K, Wn, G, lane);
+    else if (w.nc == 4) near_t_item<R, 4>(w, K, Wn, G, lane);
+    else near_t_item<R, 8>(w, K, Wn, G, lane);
+  }
+}
+
 struct DevMem {
   void* p = nullptr;
   ~DevMem() { if (p) (void)hipFree(p); }
@@ -250,6 +380,12 @@ struct sctl_amd_near {
   DevMem F_m, U_m;              // [nd_cap] densities and potentials of the host entry
   PinMem stage_m;
   int nd_cap = 0;
+  // transposed application: the element shapes are kept on the host, the work list and the gathered weights are made on the first
+  // transposed call, never by sctl_amd_near_create
+  std::vector<int64_t> e_nds, e_near, e_kcnt;
+  DevMem work_t, Wn;            // work_t: the split items, then the wave items; Wn: W in near-list order, [n_near * k1]
+  int64_t n_split = 0, n_wave_t = 0;
+  bool t_ready = false;
   hipStream_t st = nullptr;
   ~sctl_amd_near() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -328,6 +464,87 @@ int apply_densities_on_stream(sctl_amd_near* h, int nd, const R* F, R* U, hipStr
   return SCTL_AMD_OK;
 }
 
+// The transposed work list.  Lanes per row: 64 from 64 columns on; below that the power of two (at least 8, or the first one that holds
+// the row when it has fewer than 8 columns) that leaves the fewest idle lane slots over the row's passes, the widest of equals: 33 columns
+// take 5 passes of 8 lanes (8 rows per wave and step), 63 take 2 passes of 32.
+void build_transpose_work(const sctl_amd_near* h, std::vector<NearWorkT>& split, std::vector<NearWorkT>& wave) {
+  int64_t f_len = 0, n_near = 0, k_len = 0;
+  for (int64_t e = 0; e < h->nelem; e++) {
+    const int64_t sd = h->e_nds[(size_t)e] * h->k0, td = h->e_near[(size_t)e] * h->k1, kc = h->e_kcnt[(size_t)e];
+    if (kc != 0 && sd > 0 && td > 0) {
+      NearWorkT w{k_len * h->k0 * h->k1, f_len, n_near * h->k1, (int32_t)sd, (int32_t)td, 0, 0, 6, 1};
+      if (td >= kSplitCols) {
+        // fewer than 8 rows: the loads go along the row, as many 64-column chunks in flight as a wave's run of columns fills (8, or 4 and then
+        // two rows per item)
+        const int64_t per = ((td + kCols - 1) / kCols + kRowGroups - 1) / kRowGroups;   // chunks per wave, as near_gemv_t_kernel cuts the row
+        w.nc = sd >= 8 ? 1 : per >= 8 ? 8 : 4;                                          // (kSplitCols columns: at least 4 chunks per wave)
+        const int64_t rows = 8 / w.nc;
+        for (int64_t r = 0; r < sd; r += rows) { w.r0 = (int32_t)r; w.r1 = (int32_t)(r + rows < sd ? r + rows : sd); split.push_back(w); }
+      } else {
+        int lw = 6;
+        if (td < 8) { lw = 0; while ((1 << lw) < td) lw++; }
+        else if (td < kCols) {
+          int64_t best = 0;
+          for (int c = 3; c <= 5; c++) {
+            const int64_t W = 1 << c, padded = (td + W - 1) / W * W;
+            if (best == 0 || padded <= best) { best = padded; lw = c; }
+          }
+        }
+        const int64_t W = 1 << lw, step = kCols / W, passes = (td + W - 1) / W;
+        int nc = 1;
+        while (nc < 8 && (8 / nc) * step > sd) nc *= 2;      // few rows: fill the 8 loads along the row
+        while (nc > 1 && nc > passes) nc /= 2;
+        const int64_t batch = (8 / nc) * step;                 // rows of one pass of the wave
+        int64_t rows = batch * (4096 / (batch * td) > 1 ? 4096 / (batch * td) : 1);   // about 4096 entries per item
+        w.lw = lw; w.nc = nc;
+        for (int64_t r = 0; r < sd; r += rows) { w.r0 = (int32_t)r; w.r1 = (int32_t)(r + rows < sd ? r + rows : sd); wave.push_back(w); }
+      }
+    }
+    f_len += sd;
+    n_near += h->e_near[(size_t)e];
+    k_len += kc;
+  }
+}
+
+int prepare_transpose(sctl_amd_near* h, hipStream_t st) {
+  if (h->t_ready) return SCTL_AMD_OK;
+  std::vector<NearWorkT> work, wave;
+  build_transpose_work(h, work, wave);
+  h->n_split = (int64_t)work.size(); h->n_wave_t = (int64_t)wave.size();
+  work.insert(work.end(), wave.begin(), wave.end());
+  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  NEAR_TRY(h->work_t.realloc(work.size() * sizeof(NearWorkT)));
+  NEAR_TRY(h->Wn.realloc((size_t)h->n_near * h->k1 * rs));
+  if (!work.empty()) NEAR_TRY(hipMemcpy(h->work_t.p, work.data(), work.size() * sizeof(NearWorkT), hipMemcpyHostToDevice));
+  // (every entry of Wn is written by the gather when near_scatter_index is a permutation; zero otherwise.  On the caller's stream, as U_near_m)
+  NEAR_TRY(hipMemsetAsync(h->Wn.p, 0, (size_t)h->n_near * h->k1 * rs, st));
+  h->t_ready = true;
+  return SCTL_AMD_OK;
+}
+
+template <class R>
+int apply_transpose_on_stream(sctl_amd_near* h, const R* W, R* G, hipStream_t st) {
+  (void)hipGetLastError();
+  if (h->n_split + h->n_wave_t == 0) return SCTL_AMD_OK;
+  const int64_t n = h->ntrg * h->k1;
+  hipLaunchKernelGGL((near_gather_kernel<R>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->ntrg, h->k1, (const int64_t*)h->scatter.p,
+                     (const int64_t*)h->trg_cnt.p, (const int64_t*)h->trg_dsp.p, W, (R*)h->Wn.p);
+  NEAR_TRY(hipGetLastError());
+  const int64_t resident = (int64_t)h->cus * 8;
+  const int64_t groups = h->n_split + (h->n_wave_t + kRowGroups - 1) / kRowGroups;
+  const unsigned grid = (unsigned)(groups < resident * 4 ? groups : resident * 4);
+  const NearWorkT* wl = (const NearWorkT*)h->work_t.p;
+  hipLaunchKernelGGL((near_gemv_t_kernel<R>), dim3(grid), dim3(kNearBlock), 0, st, wl, h->n_split, wl + h->n_split, h->n_wave_t, (const R*)h->K.p, (const R*)h->Wn.p, G);
+  NEAR_TRY(hipGetLastError());
+  return SCTL_AMD_OK;
+}
+
+int check_apply_transpose(const sctl_amd_near* h, const void* W, const void* G) {
+  if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
+  if ((h->ntrg > 0 && !W) || (h->f_len > 0 && !G)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or density-gradient array");
+  return SCTL_AMD_OK;
+}
+
 int check_apply_densities(const sctl_amd_near* h, int nd, const void* F, const void* U) {
   if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
   if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
@@ -392,6 +609,12 @@ int sctl_amd_near_create(int real, int device, int64_t Nelem, int src_dim, int t
   std::unique_ptr<sctl_amd_near> h(new sctl_amd_near);
   h->real = real; h->device = device; h->k0 = src_dim; h->k1 = trg_dim;
   h->nelem = Nelem; h->ntrg = Ntrg; h->n_near = n_near; h->f_len = f_len; h->k_len = k_len * src_dim * trg_dim; h->nwork = (int64_t)work.size(); h->n_wide = n_wide; h->n_narrow = n_narrow;
+  if (Nelem > 0) {
+    h->e_nds.assign(elem_nds_cnt, elem_nds_cnt + Nelem);
+    h->e_near.assign(near_elem_cnt, near_elem_cnt + Nelem);
+    h->e_kcnt.resize((size_t)Nelem);
+    for (int64_t e = 0; e < Nelem; e++) h->e_kcnt[(size_t)e] = K_near_cnt ? K_near_cnt[e] : elem_nds_cnt[e] * near_elem_cnt[e];
+  }
   DeviceScope dev_scope_1(device);
   NEAR_TRY(dev_scope_1.err);
   NEAR_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
@@ -486,6 +709,48 @@ int sctl_amd_near_apply_densities_host(sctl_amd_near* h, int nd, const void* F, 
   const int64_t n = (int64_t)nd * h->ntrg * h->k1;         // every row: U += near field
   if (h->real == SCTL_AMD_F64) { double* d = (double*)U; const double* s = (const double*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
   else { float* d = (float*)U; const float* s = (const float*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_near_apply_transpose_device(sctl_amd_near* h, const void* W, void* G, void* stream) {
+  const int rc0 = check_apply_transpose(h, W, G);
+  if (rc0) return rc0;
+  if (h->k_len == 0 || h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  const int rc = prepare_transpose(h, (hipStream_t)stream);
+  if (rc) return rc;
+  if (h->real == SCTL_AMD_F64) return apply_transpose_on_stream<double>(h, (const double*)W, (double*)G, (hipStream_t)stream);
+  return apply_transpose_on_stream<float>(h, (const float*)W, (float*)G, (hipStream_t)stream);
+}
+
+int sctl_amd_near_apply_transpose_host(sctl_amd_near* h, const void* W, void* G) {
+  const int rc0 = check_apply_transpose(h, W, G);
+  if (rc0) return rc0;
+  if (h->k_len == 0 || h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t bf = (size_t)h->f_len * rs, bu = (size_t)h->ntrg * h->k1 * rs;
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  char* sf = (char*)h->stage.p;                            // the staging and the device arrays of the forward host entry, roles swapped
+  char* su = sf + ((bf + 255) & ~(size_t)255);
+  std::memcpy(su, W, bu);
+  NEAR_TRY(hipMemcpyAsync(h->U.p, su, bu, hipMemcpyHostToDevice, h->st));
+  NEAR_TRY(hipMemsetAsync(h->F.p, 0, bf, h->st));
+  const int rc = sctl_amd_near_apply_transpose_device(h, h->U.p, h->F.p, h->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  NEAR_TRY(hipMemcpyAsync(sf, h->F.p, bf, hipMemcpyDeviceToHost, h->st));
+  NEAR_TRY(hipStreamSynchronize(h->st));
+  // G += N^T W over the entries some block owns; the entries of elements without a matrix or without near targets keep their bits (a -0.0 too)
+  int64_t f_off = 0;
+  for (int64_t e = 0; e < h->nelem; e++) {
+    const int64_t sd = h->e_nds[(size_t)e] * h->k0;
+    if (h->e_kcnt[(size_t)e] != 0 && h->e_near[(size_t)e] > 0) {
+      if (h->real == SCTL_AMD_F64) { double* d = (double*)G; const double* s = (const double*)sf; for (int64_t i = f_off; i < f_off + sd; i++) d[i] += s[i]; }
+      else { float* d = (float*)G; const float* s = (const float*)sf; for (int64_t i = f_off; i < f_off + sd; i++) d[i] += s[i]; }
+    }
+    f_off += sd;
+  }
   return SCTL_AMD_OK;
 }
 
