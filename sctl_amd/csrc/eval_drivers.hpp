@@ -1,0 +1,98 @@
+// The launch planners and drivers of the all-pairs evaluators (eval_drivers.hip).  A driver takes `real` and untyped device pointers and enqueues on a
+// stream; the typed templates behind it are private to eval_drivers.hip.
+#pragma once
+#include "internal.hpp"
+#include "multi_kernel.hpp"
+
+namespace sctl_amd {
+// centered.hip
+template <class R>
+hipError_t eval_centered(int kernel_id, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, R* v_trg, double scale, int mode,
+                         int cus, hipStream_t st, bool presorted, int64_t density);
+void centered_plan(int64_t Nt, int64_t Ns, int cus, int src_bytes, int out_bytes, int* T, int* splits, int64_t* chunk);
+int centered_pipe(int kernel_id, int real, int mode);
+int centered_targets_per_wave(int kernel_id, int real, int mode, int64_t density);
+hipError_t morton_order_device(int real, const void* d_x, int64_t n, void* d_sorted, uint32_t* d_perm, hipStream_t st);
+}  // namespace sctl_amd
+
+#pragma GCC visibility push(hidden)
+namespace sctl_amd {
+
+int cu_count();   // CUs of the current device; 256 (MI355X) when planning without a device
+
+struct Plan {
+  int t_idx;        // index into kTvalues
+  int splits;
+  int64_t chunk;    // sources per split (multiple of kTile)
+  int64_t wg_x;
+  int64_t workspace_bytes;
+};
+Plan make_plan(const KernelEntry& k, int real, int64_t Nt, int64_t Ns);
+
+// The transposed evaluation (eval_transpose_kernel.hpp): make_plan with the roles exchanged — the SOURCES own the output and tile grid.x, the TARGET
+// range is split.  The partial sums [splits][owners * K0] are bounded at 2 GB by cutting the owners into several launches of owners_per_launch
+// (a multiple of a workgroup's 256 * T owners), never by taking fewer splits: the splits are what keeps a streamed chunk in one XCD's L2.
+struct PlanT {
+  int t_idx;        // index into kTTvalues
+  int splits;
+  int64_t chunk;    // targets per split (multiple of kTile)
+  int64_t owners_per_launch;
+  int64_t workspace_bytes;
+};
+PlanT make_plan_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns);
+// The geometry shared by the owner schemes that stream the other set (the transposed and the gradient evaluators): `owners` points own `out_width` sums
+// each, t per lane; the `streamed` points, `streamed_reals` reals each, are split.
+struct PlanOwned {
+  int splits;
+  int64_t chunk, owners_per_launch, workspace_bytes;
+};
+PlanOwned plan_owned(int64_t owners, int64_t streamed, int t, int64_t streamed_reals, int64_t out_width, int64_t rs);
+PlanOwned make_plan_g(const KernelEntry& k, int real, int side, int64_t Nt, int64_t Ns);
+
+// ---- several densities against one geometry (multi_kernel.hpp) ----
+const MultiEntry* multi_entry(int kernel_id);   // null for a registered plugin kernel: it is evaluated one density at a time
+int multi_form(const MultiEntry& me, int left); // the form for `left` densities still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
+struct MultiPlan {
+  int form, M, T, splits;
+  int64_t chunk, nt_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the targets of one launch of nt_launch targets
+};
+MultiPlan make_plan_multi(const KernelEntry& k, const MultiEntry& me, int form, int real, int64_t Nt, int64_t Ns);
+
+// ---- the tile-centred fast path (centered.hip) ----
+// mode < 0: the mode of the default accuracy request (what an operator handle sorts its targets for)
+bool has_centered_path(const KernelEntry& k, int real, int mode = -1);
+constexpr int64_t kPresortMinTargets = 1 << 17;   // sctl_amd_op_* keeps the targets of such kernels in Morton order from this size on
+// nt_whole: size of the target set the Nt targets were cut from as a spatially compact slab (= Nt for a whole set)
+bool use_centered(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, int64_t nt_whole = 0, bool presorted = false, int mode = -1);
+
+bool has_transpose(const KernelEntry& k);
+int no_transpose(const KernelEntry& k);   // sets the error text, returns SCTL_AMD_ERR_UNKNOWN_KERNEL
+bool has_grad(const KernelEntry& k);
+int no_grad(const KernelEntry& k);
+
+// ---- drivers: device arrays, enqueued on st; results are accumulated into ----
+// v[t,k1] += scale * sum_s U(x_t - x_s, n_s)[k0][k1] f[s,k0]
+int eval_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, void* v, int digits,
+                const void* ctx, hipStream_t st, int64_t nt_whole = 0, bool presorted = false);
+// nd >= 2 densities, density-major (a single density must take eval_device: this one would run it on the 2-density form)
+int eval_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, void* v,
+                          int digits, const void* ctx, hipStream_t st, int64_t nt_whole = 0, bool presorted = false);
+// g[s,k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] w[t,k1]
+int eval_transpose_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* w, void* g,
+                          int digits, const void* ctx, hipStream_t st);
+// g_trg, g_src, g_nrm += the gradients of <w, A f> with respect to the target coordinates, the source coordinates and the source normals; a null output is
+// not computed, and a side whose outputs are all null is not launched
+int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* w,
+                     void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st);
+int matrix_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, void* M, int digits, const void* ctx,
+                  hipStream_t st);
+void matrix_batch_launch(const KernelEntry& k, int real, const MatTile* tiles, int64_t ntiles, const void* xt, const void* xs, const void* xn, void* M,
+                         int digits, const void* ctx, hipStream_t st);
+
+// ---- the operator handle's small pre/post kernels, one launch per density row (rows `stride` reals apart); the caller asks hipGetLastError ----
+void scale_density(int real, void* f, const void* w, int64_t Ns, int k0, int nd, hipStream_t st);                     // f[m][s][:] *= w[s]
+void normal_dot(int real, const void* v, const void* nrm, void* u, int64_t nt, int k1r, int nd, hipStream_t st);     // u[m][t][k] = sum_l v[m][t][k*3+l] nrm[t][l]
+void normal_expand(int real, const void* w, const void* nrm, void* wf, int64_t nt, int k1r, hipStream_t st);         // its adjoint, one row
+
+}  // namespace sctl_amd
+#pragma GCC visibility pop

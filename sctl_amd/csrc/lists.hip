@@ -187,7 +187,7 @@ int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t n
   }
   // Each direction checks its own ownership rule only.  The streamed arrays of the forward side are r_src, n_src and v_src, those of the transposed side
   // r_trg and w_trg: the widest of them bounds the 32-bit byte offsets of the packed form.
-  const int64_t rs = real == SCTL_AMD_F64 ? 8 : 4;
+  const int64_t rs = (int64_t)real_size(real);
   SidePlan plans[2];
   if (directions & SCTL_AMD_LISTS_FORWARD) {
     const int rc = plan_side(nlists, trg_off, trg_cnt, src_off, src_cnt, Ns, rs * std::max<int64_t>(3, std::max<int64_t>(k->nd, k->k0)), "target", plans[0]);
@@ -286,8 +286,7 @@ int sctl_amd_lists_eval_device(sctl_amd_lists* p, const void* r_trg, const void*
   if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
   const ListsSide& fw = p->side[0];
   const KernelEntry& k = *p->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device: launch there whatever the caller's current device is
@@ -295,17 +294,15 @@ int sctl_amd_lists_eval_device(sctl_amd_lists* p, const void* r_trg, const void*
   (void)hipGetLastError();
   const int mode = mode_for(p->real, digits);
   const double scale = k.scale / k.acc_factor[mode];
-  if (p->real == SCTL_AMD_F64) {
-    ListArgs<double> a{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, (const double*)r_trg, (const double*)r_src, (const double*)n_src,
-                       (const double*)v_src, (double*)v_trg, scale, make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
+  with_real(p->real, [&](auto zero) {
+    using R = decltype(zero);
+    ListArgs<R> a{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, (const R*)r_trg, (const R*)r_src, (const R*)n_src,
+                  (const R*)v_src, (R*)v_trg, (R)scale, make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
     std::memcpy(a.xcd_first, fw.xcd_first, sizeof a.xcd_first);
-    k.lists_f64[mode](a, fw.nblocks, (hipStream_t)stream);
-  } else {
-    ListArgs<float> a{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, (const float*)r_trg, (const float*)r_src, (const float*)n_src,
-                      (const float*)v_src, (float*)v_trg, (float)scale, make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
-    std::memcpy(a.xcd_first, fw.xcd_first, sizeof a.xcd_first);
-    k.lists_f32[mode](a, fw.nblocks, (hipStream_t)stream);
-  }
+    if constexpr (std::is_same<R, double>::value) k.lists_f64[mode](a, fw.nblocks, (hipStream_t)stream);
+    else k.lists_f32[mode](a, fw.nblocks, (hipStream_t)stream);
+    return 0;
+  });
   LISTS_TRY(hipGetLastError());
   count_work(fw.pairs, k);
   return SCTL_AMD_OK;
@@ -316,11 +313,10 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
   if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
   const KernelEntry& k = *p->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
-  const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(p->real);
   const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
   const void* src[4] = {r_trg, r_src, n_src, v_src};
   DeviceScope scope(p->device);
@@ -335,7 +331,7 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
       p->dcap[i] = bytes[i];
     }
   }
-  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (capi.hip: PinnedBuf explains why)
+  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
     if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
     LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
     p->pinned_cap = total;
@@ -355,9 +351,7 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
   char* back = cut.take<char>(bytes[4]);
   LISTS_TRY(hipMemcpyAsync(back, p->dbuf[4], bytes[4], hipMemcpyDeviceToHost, p->st));
   LISTS_TRY(hipStreamSynchronize(p->st));
-  const int64_t n = p->Nt * k.k1;      // v_trg += device result (accumulate semantics of GenericKernel::Eval)
-  if (p->real == SCTL_AMD_F64) { double* o = (double*)v_trg; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
-  else { float* o = (float*)v_trg; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  add_into(p->real, v_trg, back, p->Nt * k.k1);      // v_trg += device result (accumulate semantics of GenericKernel::Eval)
   return SCTL_AMD_OK;
 }
 
@@ -370,8 +364,7 @@ int sctl_amd_lists_eval_transpose_device(sctl_amd_lists* p, const void* r_trg, c
   if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
   const ListsSide& tr = p->side[1];
   const KernelEntry& k = *p->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (tr.nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
   DeviceScope scope(p->device);
@@ -379,17 +372,15 @@ int sctl_amd_lists_eval_transpose_device(sctl_amd_lists* p, const void* r_trg, c
   (void)hipGetLastError();
   const int mode = mode_for(p->real, digits);
   const double scale = k.scale / k.acc_factor[mode];
-  if (p->real == SCTL_AMD_F64) {
-    ListTArgs<double> a{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, (const double*)r_src, (const double*)n_src, (const double*)r_trg,
-                        (const double*)w_trg, (double*)g_src, scale, make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
+  with_real(p->real, [&](auto zero) {
+    using R = decltype(zero);
+    ListTArgs<R> a{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, (const R*)r_src, (const R*)n_src, (const R*)r_trg,
+                   (const R*)w_trg, (R*)g_src, (R)scale, make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
     std::memcpy(a.xcd_first, tr.xcd_first, sizeof a.xcd_first);
-    k.lists_t_f64[mode](a, tr.nblocks, (hipStream_t)stream);
-  } else {
-    ListTArgs<float> a{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, (const float*)r_src, (const float*)n_src, (const float*)r_trg,
-                       (const float*)w_trg, (float*)g_src, (float)scale, make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
-    std::memcpy(a.xcd_first, tr.xcd_first, sizeof a.xcd_first);
-    k.lists_t_f32[mode](a, tr.nblocks, (hipStream_t)stream);
-  }
+    if constexpr (std::is_same<R, double>::value) k.lists_t_f64[mode](a, tr.nblocks, (hipStream_t)stream);
+    else k.lists_t_f32[mode](a, tr.nblocks, (hipStream_t)stream);
+    return 0;
+  });
   LISTS_TRY(hipGetLastError());
   count_work(tr.pairs, k);
   return SCTL_AMD_OK;
@@ -400,11 +391,10 @@ int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* p, const void* r_trg, con
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
   if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
   const KernelEntry& k = *p->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (p->side[1].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
-  const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(p->real);
   // the forward entry's buffers with the roles of the last two exchanged: [3] (the size of v_src) receives g_src, [4] (the size of v_trg) holds w_trg
   const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
   const void* src[5] = {r_trg, r_src, n_src, nullptr, w_trg};
@@ -420,7 +410,7 @@ int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* p, const void* r_trg, con
       p->dcap[i] = bytes[i];
     }
   }
-  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (capi.hip: PinnedBuf explains why)
+  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
     if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
     LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
     p->pinned_cap = total;
@@ -441,9 +431,7 @@ int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* p, const void* r_trg, con
   if (rc != SCTL_AMD_OK) return rc;
   LISTS_TRY(hipMemcpyAsync(back, p->dbuf[3], bytes[3], hipMemcpyDeviceToHost, p->st));
   LISTS_TRY(hipStreamSynchronize(p->st));
-  const int64_t n = p->Ns * k.k0;      // g_src += device result
-  if (p->real == SCTL_AMD_F64) { double* o = (double*)g_src; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
-  else { float* o = (float*)g_src; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  add_into(p->real, g_src, back, p->Ns * k.k0);      // g_src += device result
   return SCTL_AMD_OK;
 }
 
@@ -494,8 +482,7 @@ int check_lists_densities(const sctl_amd_lists* p, int nd, const void* ctx, int 
   if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
   if (!(p->directions & SCTL_AMD_LISTS_FORWARD)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the FORWARD direction");
   const KernelEntry& k = *p->k;
-  if (k.ctx_bytes != 0 && (ctx_bytes != k.ctx_bytes || !ctx))
-    return set_error(SCTL_AMD_ERR_BAD_CONTEXT, std::string(k.name) + " needs a context blob of " + std::to_string(k.ctx_bytes) + " bytes");
+  if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   return SCTL_AMD_OK;
 }
 
@@ -545,11 +532,7 @@ int sctl_amd_lists_eval_densities_device(sctl_amd_lists* p, int nd, const void* 
   if (!r_trg || !r_src || !v_src || !v_trg || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device
   LISTS_TRY(scope.err);
-  if (p->real == SCTL_AMD_F64)
-    return lists_eval_densities_t<double>(p, nd, (const double*)r_trg, (const double*)r_src, (const double*)n_src, (const double*)v_src, (double*)v_trg, digits,
-                                          ctx, ctx_bytes, (hipStream_t)stream);
-  return lists_eval_densities_t<float>(p, nd, (const float*)r_trg, (const float*)r_src, (const float*)n_src, (const float*)v_src, (float*)v_trg, digits, ctx,
-                                       ctx_bytes, (hipStream_t)stream);
+  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_densities_t<R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)v_src, (R*)v_trg, digits, ctx, ctx_bytes, (hipStream_t)stream); });
 }
 
 // Coordinates and normals go down once, the nd density rows in one transfer, the nd result rows come back in one; the handle's device buffers
@@ -562,7 +545,7 @@ int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_
   if (nd == 0 || p->side[0].nitems == 0) return SCTL_AMD_OK;
   const KernelEntry& k = *p->k;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
-  const size_t rs = (p->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(p->real);
   const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
   const void* src[4] = {r_trg, r_src, n_src, v_src};
   DeviceScope scope(p->device);
@@ -598,9 +581,7 @@ int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_
   char* back = cut.take<char>(bytes[4]);
   LISTS_TRY(hipMemcpyAsync(back, p->dbuf[4], bytes[4], hipMemcpyDeviceToHost, p->st));
   LISTS_TRY(hipStreamSynchronize(p->st));
-  const int64_t n = (int64_t)nd * p->Nt * k.k1;      // v_trg += device result, every row
-  if (p->real == SCTL_AMD_F64) { double* o = (double*)v_trg; const double* s = (const double*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
-  else { float* o = (float*)v_trg; const float* s = (const float*)back; for (int64_t i = 0; i < n; i++) o[i] += s[i]; }
+  add_into(p->real, v_trg, back, (int64_t)nd * p->Nt * k.k1);      // v_trg += device result, every row
   return SCTL_AMD_OK;
 }
 

@@ -3,6 +3,7 @@
 // (boundary_integral.txx:1092-1102), the permutation by near_scatter_index (:1129) and the per-target accumulation
 // (:1131-1140).  HBM-bound: every byte of K_near is read exactly once per application and nothing else is of that order.
 #include <sctl_amd.h>
+#include "staging.hpp"
 #include "workspace.hpp"
 
 #include <hip/hip_runtime.h>
@@ -14,7 +15,7 @@
 #include <vector>
 
 namespace sctl_amd {
-int set_error(int code, const std::string& msg);   // capi.hip: records the message for sctl_amd_last_error()
+int set_error(int code, const std::string& msg);   // capi.hip (internal.hpp): records the message for sctl_amd_last_error()
 
 namespace {
 
@@ -512,7 +513,7 @@ int prepare_transpose(sctl_amd_near* h, hipStream_t st) {
   build_transpose_work(h, work, wave);
   h->n_split = (int64_t)work.size(); h->n_wave_t = (int64_t)wave.size();
   work.insert(work.end(), wave.begin(), wave.end());
-  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(h->real);
   NEAR_TRY(h->work_t.realloc(work.size() * sizeof(NearWorkT)));
   NEAR_TRY(h->Wn.realloc((size_t)h->n_near * h->k1 * rs));
   if (!work.empty()) NEAR_TRY(hipMemcpy(h->work_t.p, work.data(), work.size() * sizeof(NearWorkT), hipMemcpyHostToDevice));
@@ -605,7 +606,7 @@ int sctl_amd_near_create(int real, int device, int64_t Nelem, int src_dim, int t
   if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }
   if (ndev <= 0 || device < 0 || device >= ndev) return set_error(SCTL_AMD_ERR_NO_DEVICE, "no HIP device: libsctl_amd has no CPU fallback");
 
-  const size_t rs = (real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(real);
   std::unique_ptr<sctl_amd_near> h(new sctl_amd_near);
   h->real = real; h->device = device; h->k0 = src_dim; h->k1 = trg_dim;
   h->nelem = Nelem; h->ntrg = Ntrg; h->n_near = n_near; h->f_len = f_len; h->k_len = k_len * src_dim * trg_dim; h->nwork = (int64_t)work.size(); h->n_wide = n_wide; h->n_narrow = n_narrow;
@@ -644,30 +645,27 @@ int sctl_amd_near_create(int real, int device, int64_t Nelem, int src_dim, int t
 int sctl_amd_near_apply_device(sctl_amd_near* h, const void* F, void* U, void* stream) {
   if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
   if ((h->f_len > 0 && !F) || (h->ntrg > 0 && !U)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
-  if (h->real == SCTL_AMD_F64) return apply_on_stream<double>(h, (const double*)F, (double*)U, (hipStream_t)stream);
-  return apply_on_stream<float>(h, (const float*)F, (float*)U, (hipStream_t)stream);
+  return with_real(h->real, [&](auto zero) { using R = decltype(zero); return apply_on_stream<R>(h, (const R*)F, (R*)U, (hipStream_t)stream); });
 }
 
 int sctl_amd_near_apply_host(sctl_amd_near* h, const void* F, void* U) {
   if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
   if ((h->f_len > 0 && !F) || (h->ntrg > 0 && !U)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or potential array");
   if (h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
-  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(h->real);
   const size_t bf = (size_t)h->f_len * rs, bu = (size_t)h->ntrg * h->k1 * rs;
   DeviceScope dev_scope_2(h->device);
   NEAR_TRY(dev_scope_2.err);
   char* sf = (char*)h->stage.p;
   char* su = sf + ((bf + 255) & ~(size_t)255);
-  std::memcpy(sf, F, bf);                                  // pinned staging: see capi.hip PinnedBuf
+  std::memcpy(sf, F, bf);                                  // pinned staging: see staging.hpp PinnedBufT
   NEAR_TRY(hipMemcpyAsync(h->F.p, sf, bf, hipMemcpyHostToDevice, h->st));
   NEAR_TRY(hipMemsetAsync(h->U.p, 0, bu, h->st));
   const int rc = sctl_amd_near_apply_device(h, h->F.p, h->U.p, h->st);
   if (rc != SCTL_AMD_OK) return rc;
   NEAR_TRY(hipMemcpyAsync(su, h->U.p, bu, hipMemcpyDeviceToHost, h->st));
   NEAR_TRY(hipStreamSynchronize(h->st));
-  const int64_t n = h->ntrg * h->k1;                       // U += near field (boundary_integral.txx:1131-1140)
-  if (h->real == SCTL_AMD_F64) { double* d = (double*)U; const double* s = (const double*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
-  else { float* d = (float*)U; const float* s = (const float*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
+  add_into(h->real, U, su, h->ntrg * h->k1);                       // U += near field (boundary_integral.txx:1131-1140)
   return SCTL_AMD_OK;
 }
 
@@ -677,8 +675,7 @@ int sctl_amd_near_apply_densities_device(sctl_amd_near* h, int nd, const void* F
   if (nd == 1) return sctl_amd_near_apply_device(h, F, U, stream);
   DeviceScope dev_scope(h->device);
   NEAR_TRY(dev_scope.err);
-  if (h->real == SCTL_AMD_F64) return apply_densities_on_stream<double>(h, nd, (const double*)F, (double*)U, (hipStream_t)stream);
-  return apply_densities_on_stream<float>(h, nd, (const float*)F, (float*)U, (hipStream_t)stream);
+  return with_real(h->real, [&](auto zero) { using R = decltype(zero); return apply_densities_on_stream<R>(h, nd, (const R*)F, (R*)U, (hipStream_t)stream); });
 }
 
 int sctl_amd_near_apply_densities_host(sctl_amd_near* h, int nd, const void* F, void* U) {
@@ -686,7 +683,7 @@ int sctl_amd_near_apply_densities_host(sctl_amd_near* h, int nd, const void* F, 
   if (rc0 || nd == 0) return rc0;
   if (nd == 1) return sctl_amd_near_apply_host(h, F, U);
   if (h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
-  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(h->real);
   const size_t bf = (size_t)nd * h->f_len * rs, bu = (size_t)nd * h->ntrg * h->k1 * rs;
   DeviceScope dev_scope(h->device);
   NEAR_TRY(dev_scope.err);
@@ -706,9 +703,7 @@ int sctl_amd_near_apply_densities_host(sctl_amd_near* h, int nd, const void* F, 
   if (rc != SCTL_AMD_OK) return rc;
   NEAR_TRY(hipMemcpyAsync(su, h->U_m.p, bu, hipMemcpyDeviceToHost, h->st));
   NEAR_TRY(hipStreamSynchronize(h->st));
-  const int64_t n = (int64_t)nd * h->ntrg * h->k1;         // every row: U += near field
-  if (h->real == SCTL_AMD_F64) { double* d = (double*)U; const double* s = (const double*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
-  else { float* d = (float*)U; const float* s = (const float*)su; for (int64_t i = 0; i < n; i++) d[i] += s[i]; }
+  add_into(h->real, U, su, (int64_t)nd * h->ntrg * h->k1);         // every row: U += near field
   return SCTL_AMD_OK;
 }
 
@@ -720,15 +715,14 @@ int sctl_amd_near_apply_transpose_device(sctl_amd_near* h, const void* W, void* 
   NEAR_TRY(dev_scope.err);
   const int rc = prepare_transpose(h, (hipStream_t)stream);
   if (rc) return rc;
-  if (h->real == SCTL_AMD_F64) return apply_transpose_on_stream<double>(h, (const double*)W, (double*)G, (hipStream_t)stream);
-  return apply_transpose_on_stream<float>(h, (const float*)W, (float*)G, (hipStream_t)stream);
+  return with_real(h->real, [&](auto zero) { using R = decltype(zero); return apply_transpose_on_stream<R>(h, (const R*)W, (R*)G, (hipStream_t)stream); });
 }
 
 int sctl_amd_near_apply_transpose_host(sctl_amd_near* h, const void* W, void* G) {
   const int rc0 = check_apply_transpose(h, W, G);
   if (rc0) return rc0;
   if (h->k_len == 0 || h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
-  const size_t rs = (h->real == SCTL_AMD_F64) ? 8 : 4;
+  const size_t rs = real_size(h->real);
   const size_t bf = (size_t)h->f_len * rs, bu = (size_t)h->ntrg * h->k1 * rs;
   DeviceScope dev_scope(h->device);
   NEAR_TRY(dev_scope.err);
@@ -746,8 +740,7 @@ int sctl_amd_near_apply_transpose_host(sctl_amd_near* h, const void* W, void* G)
   for (int64_t e = 0; e < h->nelem; e++) {
     const int64_t sd = h->e_nds[(size_t)e] * h->k0;
     if (h->e_kcnt[(size_t)e] != 0 && h->e_near[(size_t)e] > 0) {
-      if (h->real == SCTL_AMD_F64) { double* d = (double*)G; const double* s = (const double*)sf; for (int64_t i = f_off; i < f_off + sd; i++) d[i] += s[i]; }
-      else { float* d = (float*)G; const float* s = (const float*)sf; for (int64_t i = f_off; i < f_off + sd; i++) d[i] += s[i]; }
+      add_into(h->real, (char*)G + (size_t)f_off * rs, sf + (size_t)f_off * rs, sd);
     }
     f_off += sd;
   }
@@ -760,7 +753,7 @@ int sctl_amd_near_info(const sctl_amd_near* h, int64_t* density_len, int64_t* po
   if (density_len) *density_len = h->f_len;
   if (potential_len) *potential_len = h->ntrg * h->k1;
   if (near_entries) *near_entries = h->n_near;
-  if (operator_bytes) *operator_bytes = h->k_len * ((h->real == SCTL_AMD_F64) ? 8 : 4);
+  if (operator_bytes) *operator_bytes = h->k_len * (int64_t)real_size(h->real);
   if (workgroups) *workgroups = h->nwork;
   return SCTL_AMD_OK;
 }
