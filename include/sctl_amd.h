@@ -233,6 +233,34 @@ int sctl_amd_eval_transpose_host(int kernel, int real, int64_t Nt, int64_t Ns, c
  * of one launch.  Those stay within 2 GB: the sources are cut into several launches rather than the targets into fewer splits. */
 int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* src_per_lane, int* splits, int64_t* workspace_bytes);
 
+/* ---- several weight vectors through the transposed sum: g_src[m] += A^T w_trg[m] --------------------------------------------------- */
+/* nd weight vectors on the same targets and sources in one evaluation: what nd calls of the single transposed entry compute,
+ *     g_src[m][s*SrcDim + k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] * w_trg[m][t*TrgDim + k1],   m = 0 .. nd-1,
+ * with the work of a pair that does not depend on the weights (distance, reciprocal square root, d.n, Helmholtz's e^{ikr}) done once for
+ * several of them: A^T W for the block a block BiCG / QMR / LSQR iteration sent through A V (sctl_amd_eval_densities_*), an adjoint solve
+ * for several right-hand sides, back-propagation through sctl_amd_eval_densities_*.  Layout is ROW-MAJOR as there: w_trg holds nd
+ * consecutive weight vectors, [nd][Nt*TrgDim], and g_src [nd][Ns*SrcDim]; row m is exactly what a single transposed call takes and
+ * returns.  nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, and nd == 1 IS the single transposed entry (bit-identical results,
+ * the same plan).  Argument errors return the codes of sctl_amd_eval_transpose_*, before any device work.  The built-in kernels run up to 8
+ * weight vectors per pass (4 for the traction kernel) on the exact all-pairs kernel (csrc/multi_transpose_kernel.hpp): sums in a fixed
+ * order, bit-reproducible; a registered kernel with pair_t (which has no several-vectors form) is evaluated one row at a time on the same
+ * stream, one without pair_t is SCTL_AMD_ERR_UNKNOWN_KERNEL.  fp32 runs this exact pair at every `digits`, as the single transposed entry
+ * does.  Counters grow by nd*Nt*Ns pairs.  Not provided: several weight vectors for sctl_amd_near_apply_transpose_*,
+ * sctl_amd_op_eval_transpose / _potential_transpose and the P2P lists, and any multi-GPU form. */
+/* DEVICE arrays; enqueued on `stream`; g_src is accumulated into. */
+int sctl_amd_eval_transpose_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                             const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream);
+/* HOST arrays, one device; returns when g_src is final.  accumulate != 0 adds to g_src, 0 overwrites it. */
+int sctl_amd_eval_transpose_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                           const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes, int device);
+/* The plan of such a call (no side effects, no GPU needed): weight vectors per pass of the widest pass and the number of passes (the last
+ * pass takes the narrowest form that holds what is left, one vector the form of 2), and of the first pass the sources per lane, the splits
+ * of the target range, the workgroups over all its source launches, and the largest partial-sum workspace of any pass.  The partial sums
+ * of one launch stay within 2 GB: a pass cuts its sources into several launches rather than take fewer splits than the L2 rule asks for.
+ * nd == 1 is sctl_amd_eval_transpose_plan's answer. */
+int sctl_amd_eval_transpose_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* vectors_per_pass, int* passes,
+                                           int* src_per_lane, int* splits, int64_t* workgroups, int64_t* workspace_bytes);
+
 /* ---- gradients of <w_trg, A v_src> with respect to the geometry ------------------------------------------------------------------ */
 /* With L = sum_t sum_k1 w_trg[t*TrgDim + k1] * v_trg[t*TrgDim + k1], v_trg = A v_src as sctl_amd_eval_* computes it, d = x_t - x_s and the pair's scalar
  *     phi_ts = sum_k0 sum_k1 w_trg[t*TrgDim + k1] * U(d, n_s)[k0][k1] * v_src[s*SrcDim + k0],

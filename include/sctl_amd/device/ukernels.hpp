@@ -27,6 +27,12 @@
 //   pair_t<R,MODE,MASKED[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[k0] += sum_k1 U(d, n)[k0][k1] w[k1] with the SAME d = x_trg - x_src as pair(), n the owner's
 //                              normal (R[3], or R[1] unused when ND == 0) from registers.  Same rsqrt helpers, modes, masking and acc_factor as pair().
 //   finish_t<R>(acc) / finish_t_mode<R,MODE>(acc)   optional, applied once to a source's K0 sums (FinishTOf)
+// and the transposed forms for several weight vectors used by sctl_amd/csrc/multi_transpose_kernel.hpp (M weight vectors on the same targets and sources):
+//   NREC_TM<M>                 reals per streamed target record: x_t once, then what the pair needs of each of the M weight vectors, padded to 16 bytes
+//   pack_tm<R,M>(rec, x_t, w)  w[M][K1]: the weights as they are (the traction kernel: the six symmetric sums of each); nothing mode-dependent is folded in
+//   pair_tm<R,MODE,MASKED,M[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[M][K0]: what does not depend on w (distance, reciprocal square root and its refinement,
+//                              d.n, Helmholtz's reduction and polynomial) once, then one contraction per weight vector.  Same d = x_trg - x_src, masking,
+//                              acc_factor and finish_t / finish_t_mode as pair_t(): a launch scales and finishes both forms alike.
 // and the gradient form used by eval_grad_kernel.hpp from both of its sides (the pair's scalar phi = sum_k0 sum_k1 w[k1] U(d, n)[k0][k1] f[k0]):
 //   pair_g<R,MODE,MASKED[,VARIANT],WANT_N>(G, N, d, n, f, w, ctx, K)   G[j] += d phi / d d_j and, where WANT_N, N[j] += d phi / d n_j, with the SAME
 //                              d = x_trg - x_src as pair(); n (R[3], or R[1] unused when ND == 0), f[K0] and w[K1] are the plain inputs, from registers
@@ -410,6 +416,13 @@ template <int ND, int K0, class R, int M> __device__ __forceinline__ void pack_m
   template <class R, int M> static __device__ __forceinline__ void pack_m(R* rec, const R* x, const R* n, const R (&f)[M][K0]) {      \
     pack_multi<ND, K0>(rec, x, n, f);                                                                                                 \
   }
+// ---- transposed records of several weight vectors (pack_tm / pair_tm of every struct below): x_t, then M x `per_w` reals ---------------
+constexpr int nrec_tm(int per_w, int m) { return (3 + m * per_w + 1) / 2 * 2; }
+#define SCTL_AMD_MULTI_T_RECORD                                                                                                        \
+  template <int M> static constexpr int NREC_TM = nrec_tm(K1, M);                                                                     \
+  template <class R, int M> static __device__ __forceinline__ void pack_tm(R* rec, const R* x, const R (&w)[M][K1]) {                 \
+    pack_multi<0, K1>(rec, x, (const R*)nullptr, w);                                                                                  \
+  }
 
 // ---- Laplace single layer: u = f / r          (kernel_functions.hpp:15-31) -------------------------------
 struct Laplace3D_FxU {
@@ -437,6 +450,13 @@ struct Laplace3D_FxU {
   template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) { rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; }
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(rec[3], rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq), acc[0]);
+  }
+  // transposed, several weights: 1 FMA per weight vector
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R rinv = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[3 + m], rinv, acc[m][0]);
   }
   // gradient: phi = w f y, grad_d = -(w f) y^3 d
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -473,6 +493,13 @@ struct Laplace3D_DxU {
   template <class R> static __device__ __forceinline__ void pack_t(R* rec, const R* x, const R* w) { rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2]; rec[3] = w[0]; }
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(dot3(d, n), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq) * rec[3], acc[0]);
+  }
+  // transposed, several weights: (d.n) / r^3 once, 1 FMA per weight vector
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R t = dot3(d, n) * rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq);
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m][0] = fma_(rec[3 + m], t, acc[m][0]);
   }
   // gradient: phi = c (d.n) y^3 with c = w f: grad_d = c y^3 (n - 3 (d.n) y^2 d), grad_n = c y^3 d
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -520,6 +547,14 @@ struct Laplace3D_FxdU {
   }
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     acc[0] = fma_(dot3(d, rec + 3), rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq), acc[0]);
+  }
+  // transposed, several weights: d / r^3 once, 3 FMAs per weight vector
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R t = rsqrt_pow_scaled<MODE, 3, MASKED>(len2(d), K.rsq);
+    const R td[3] = {t * d[0], t * d[1], t * d[2]};
+#pragma unroll
+    for (int m = 0; m < M; m++) acc[m][0] = fma_(td[2], rec[5 + 3 * m], fma_(td[1], rec[4 + 3 * m], fma_(td[0], rec[3 + 3 * m], acc[m][0])));
   }
   // gradient: phi = f (d.w) y^3: grad_d = f y^3 (w - 3 (d.w) y^2 d), the double layer's with w for n
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -571,6 +606,11 @@ struct Stokes3D_FxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     pair<R, MODE, MASKED>(acc, d, rec, KerCtx{}, K);
   }
+  // transposed, several weights: the block is symmetric, so pair_m with w for f (9 instructions per weight vector)
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx& ctx, const Consts<R>& K) {
+    pair_m<R, MODE, MASKED, M>(acc, d, rec, ctx, K);
+  }
   // gradient: phi = (f.w) y + (d.f)(d.w) y^3 (stokeslet_grad)
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
@@ -613,6 +653,18 @@ struct Stokes3D_DxU {
   template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_t(R (&acc)[K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
     const R t = dot3(d, n) * dot3(d, rec + 3) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
+  }
+  // transposed, several weights: (d.n) d / r^5 once, (d.w) and 3 FMAs per weight vector
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R g = dot3(d, n) * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    const R gd[3] = {g * d[0], g * d[1], g * d[2]};
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R dw = dot3(d, rec + 3 + 3 * m);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(gd[j], dw, acc[m][j]);
+    }
   }
   // gradient: phi = a b c y^5 with a = d.n, b = d.f, c = d.w: grad_d = y^5 (bc n + ac f + ab w - 5 abc y^2 d), grad_n = bc y^5 d
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -687,6 +739,37 @@ struct Stokes3D_FxT {
     const R t = q * rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
     for (int j = 0; j < 3; j++) acc[j] = fma_(t, d[j], acc[j]);
   }
+  // transposed, several weights: the six d_j d_k / r^5 once; per weight vector the quadratic form against its six symmetric sums (6 instructions) and
+  // 3 FMAs.  record x_t, then S00 S01 S02 S11 S12 S22 of each weight vector (pack_t's sums)
+  template <int M> static constexpr int NREC_TM = nrec_tm(6, M);
+  template <class R, int M> static __device__ __forceinline__ void pack_tm(R* rec, const R* x, const R (&w)[M][K1]) {
+    rec[0] = x[0]; rec[1] = x[1]; rec[2] = x[2];
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      R* s = rec + 3 + 6 * m;
+      s[0] = w[m][0]; s[1] = w[m][1] + w[m][3]; s[2] = w[m][2] + w[m][6]; s[3] = w[m][4]; s[4] = w[m][5] + w[m][7]; s[5] = w[m][8];
+    }
+  }
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R p = rsqrt_pow_scaled<MODE, 5, MASKED>(len2(d), K.rsq);
+    R dd[6];
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const R pj = p * d[j];
+#pragma unroll
+      for (int k = j; k < 3; k++) dd[q++] = pj * d[k];
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* s = rec + 3 + 6 * m;
+      R t = s[0] * dd[0];
+#pragma unroll
+      for (int i = 1; i < 6; i++) t = fma_(s[i], dd[i], t);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(t, d[j], acc[m][j]);
+    }
+  }
   // gradient: phi = A q y^5 with A = d.f and q = d^T W d, W = w[j*3+k]: with v = (W + W^T) d = grad q and q = (d.v) / 2,
   //   grad_d = y^5 (q f + A v - 5 A q y^2 d)
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -749,6 +832,22 @@ struct Stokes3D_FSxU {
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[6 + j]), acc[j]);
     acc[3] = fma_(t, y, acc[3]);
   }
+  // transposed, several weights: the velocity + pressure kernel's pair_m with w for f (10 instructions per weight vector)
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);                                  // C / r
+    const R y3 = (y * y) * y;
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));           // C^2 (C / r): the term in 1/r alone
+    const R e[3] = {y3 * d[0], y3 * d[1], y3 * d[2]};                                         // C^3 d / r^3
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* w = rec + 3 + 3 * m;
+      const R dw = dot3(d, w);
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], dw, fma_(yc, w[j], acc[m][j]));
+      acc[m][3] = fma_(y3, dw, acc[m][3]);
+    }
+  }
   // gradient: phi = (f.w) y + ((d.f) + f_3)(d.w) y^3, the Stokeslet's with A = (d.f) + f_3 (stokeslet_grad)
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
@@ -801,6 +900,21 @@ struct Stokes3D_FxUP {
     const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);
     const R t = fma_(d[2], rec[5], fma_(d[1], rec[4], fma_(d[0], rec[3], rec[6]))) * (y * y);
     for (int j = 0; j < 3; j++) acc[j] = fma_(y, fma_(t, d[j], rec[7 + j]), acc[j]);
+  }
+  // transposed, several weights: the source/sink kernel's pair_m with w for f (9 instructions per weight vector)
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);                                  // C / r
+    const R y3 = (y * y) * y;
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));           // C^2 (C / r): the term in 1/r alone
+    const R e[3] = {y3 * d[0], y3 * d[1], y3 * d[2]};                                         // C^3 d / r^3
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R* w = rec + 3 + 4 * m;
+      const R dw = fma_(d[2], w[2], fma_(d[1], w[1], fma_(d[0], w[0], w[3])));               // (d.w_u) + w_p
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc[m][j] = fma_(e[j], dw, fma_(yc, w[j], acc[m][j]));
+    }
   }
   // gradient: phi = (f.w_u) y + (d.f)((d.w_u) + w_p) y^3, the Stokeslet's with B = (d.w_u) + w_p (stokeslet_grad)
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
@@ -887,6 +1001,31 @@ struct Laplace3D_FDxUdU {
     const R e = fma_(-a, K.c3, rec[3]);                     // C^2 (w_u - 3 (d.w_g) / r^2)
     const R h = fma_(n[2], rec[9], fma_(n[1], rec[8], fma_(n[0], rec[7], dot3(d, n) * e)));
     acc[1] = fma_(y3, h, acc[1]);
+  }
+  // transposed, several weights: the record keeps (w_u, w_g) per weight vector as they are.  With y = C / r, c2 = C^2 and dn = d.n, pair_t() accumulates
+  //   g_q  += c2 y w_u - y^3 (d.w_g)                                   (finish_t_mode multiplies by c2)
+  //   g_mu += (c2 dn y^3) w_u + sum_j (c2 y^3 n_j - 3 dn y^5 d_j) w_g[j]
+  // so the eight factors are formed once (pair_m's A and B among them) and each weight vector costs 8 FMAs.
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R* rec, const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_scaled<MODE, MASKED>(len2(d), K.rsq);   // C / r
+    const R y2 = y * y;
+    const R y3 = y2 * y;
+    const R dn = dot3(d, n);
+    const R yc = (rsqrt_scaled_c2(MODE) == 1.0) ? y : y * R(rsqrt_scaled_c2(MODE));
+    const R y3c = (rsqrt_scaled_c2(MODE) == 1.0) ? y3 : y3 * R(rsqrt_scaled_c2(MODE));
+    const R g1 = dn * y3c;
+    const R a = (dn * y2) * K.c3 * y3;                      // 3 dn y^5
+    R A[3], B[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) { A[j] = fma_(y3c, n[j], -a * d[j]); B[j] = y3 * d[j]; }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R wu = rec[3 + 4 * m];
+      const R* wg = rec + 4 + 4 * m;
+      acc[m][0] = fma_(-B[2], wg[2], fma_(-B[1], wg[1], fma_(-B[0], wg[0], fma_(yc, wu, acc[m][0]))));
+      acc[m][1] = fma_(A[2], wg[2], fma_(A[1], wg[1], fma_(A[0], wg[0], fma_(g1, wu, acc[m][1]))));
+    }
   }
   // gradient: with q = f[0], mu = f[1], w_u = w[0], w_g = w[1..3], dn = d.n, B = d.w_g, nw = n.w_g the pair's scalar is
   //   phi = a1 y + P3 y^3 + P5 y^5,    a1 = w_u q,    P3 = mu (w_u dn + nw) - q B,    P5 = -3 mu dn B
@@ -1001,6 +1140,31 @@ struct Helmholtz3D_FxU {
     }
     acc[0] = fma_(gr, rec[3], fma_(gi, rec[4], acc[0]));
     acc[1] = fma_(gr, rec[4], fma_(-gi, rec[3], acc[1]));
+  }
+  // transposed, several weights: G once, as pair_t() forms it; 4 FMAs per weight vector
+  SCTL_AMD_MULTI_T_RECORD
+  template <class R, int MODE, bool MASKED, int M, int VARIANT = 0> static __device__ __forceinline__ void pair_tm(R (&acc)[M][K0], const R (&d)[3], const R (&)[1], const R* rec, const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      const R wr = rec[3 + 2 * m], wi = rec[4 + 2 * m];
+      acc[m][0] = fma_(gr, wr, fma_(gi, wi, acc[m][0]));
+      acc[m][1] = fma_(gr, wi, fma_(-gi, wr, acc[m][1]));
+    }
   }
   // gradient: with c = conj(w) f and G = e^{ikr} / r the pair's scalar is phi = Re(c G), and dG/dr = (ik - 1/r) G, so
   //   grad_d = Re((ik - y) c G) y d,    Re((ik - y) H) = -(Im k + y) H_re - (Re k) H_im,    y = 1/r

@@ -206,6 +206,29 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_transpose_host");
   }
 
+  // EvalTranspose for several weight vectors in one evaluation (sctl_amd_eval_transpose_densities_host; not in the reference): row m of W (nd x Nt*TrgDim)
+  // is a vector of target weights, row m of G (nd x Ns*SrcDim) what EvalTranspose gives for it — A^T W for the block EvalDensities sent through A — with
+  // the weight-independent work of a pair done once for several rows.  G follows EvalDensities' rule: the right size is accumulated into, any other is
+  // resized and zeroed.  nd == 1 is EvalTranspose's own path.
+  template <class Real, Integer digits = -1>
+  void EvalTransposeDensities(Matrix<Real>& G, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Matrix<Real>& W) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nd = W.Dim(0);
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(W.Dim(1) == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(nd <= 0x7fffffff);
+    if (G.Dim(0) != nd || G.Dim(1) != Ns * KDIM0) {
+      G.ReInit(nd, Ns * KDIM0);
+      G.SetZero();
+    }
+    RequireSupported();
+    const int rc = sctl_amd_eval_transpose_densities_host(DeviceKernelId(), RealTag<Real>::value, (int)nd, Nt, Ns, r_trg.begin(), r_src.begin(),
+                                                          N_DIM ? n_src.begin() : nullptr, W.begin(), G.begin(), /*accumulate*/ 1, (int)digits, ctx_ptr,
+                                                          (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_transpose_densities_host");
+  }
+
   // EvalTranspose over P2P lists (sctl_amd_eval_lists_transpose_host; not in the reference): g_src += sum over the lists of A_l^T w_trg, the adjoint of
   // EvalLists over the same lists.  The SOURCE ranges of any two lists must be identical or disjoint; target ranges may overlap.  g_src follows
   // EvalTranspose's rule: the right size is accumulated into, any other is resized and zeroed.

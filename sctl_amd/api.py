@@ -35,7 +35,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_lists_create_directions", "sctl_amd_lists_eval_transpose_device", "sctl_amd_lists_eval_transpose_host", "sctl_amd_lists_transpose_info",
            "sctl_amd_eval_lists_transpose_host",
            "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan",
-           "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose"]
+           "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose",
+           "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -142,6 +143,9 @@ def lib():
     L.sctl_amd_eval_transpose_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_transpose_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
+    L.sctl_amd_eval_transpose_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_transpose_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
+    L.sctl_amd_eval_transpose_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(i64)] * 2
     L.sctl_amd_eval_grad_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_grad_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_grad_plan.argtypes = [ci, ci, i64, i64, ci] + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)] * 2
@@ -249,6 +253,16 @@ def plan_transpose(name, real, Nt, Ns, digits=-1):
     ws = C.c_int64()
     _check(lib().sctl_amd_eval_transpose_plan(kernel_id(name), real, Nt, Ns, digits, C.byref(t), C.byref(s), C.byref(ws)), "eval_transpose_plan")
     return dict(src_per_lane=t.value, splits=s.value, workspace_bytes=ws.value)
+
+
+def plan_transpose_densities(name, real, nd, Nt, Ns, digits=-1):
+    """Launch plan of a transposed evaluation of nd weight vectors (sctl_amd_eval_transpose_densities_plan): weight vectors per pass, passes, and of
+    the first pass sources per lane, target splits, workgroups; the largest partial-sum workspace of any pass."""
+    v = [C.c_int() for _ in range(4)]
+    wg, ws = C.c_int64(), C.c_int64()
+    _check(lib().sctl_amd_eval_transpose_densities_plan(kernel_id(name), real, nd, Nt, Ns, digits, *[C.byref(x) for x in v], C.byref(wg), C.byref(ws)),
+           "eval_transpose_densities_plan")
+    return dict(vectors_per_pass=v[0].value, passes=v[1].value, src_per_lane=v[2].value, splits=v[3].value, workgroups=wg.value, workspace_bytes=ws.value)
 
 
 def plan_grad(name, real, Nt, Ns, digits=-1):
@@ -435,6 +449,52 @@ def eval_transpose_device(name, r_trg, r_src, n_src, w_trg, g_src=None, digits=-
     return g_src
 
 
+def eval_transpose_densities_host(name, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1, ctx=None, device=0, accumulate=True):
+    """nd weight vectors through the transposed sum, G_src[m] += A^T W_trg[m], on numpy arrays (sctl_amd_eval_transpose_densities_host): W_trg of
+    shape (nd, Nt*TrgDim), returns (nd, Ns*SrcDim).  A G_src of that shape is accumulated into (overwritten with accumulate=False); None (or another
+    shape) gives a fresh zeroed result."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    if W_trg.ndim != 2 or W_trg.shape[1] != Nt * info["k1"]:
+        raise SctlAmdError("W_trg must have shape (nd, %d)" % (Nt * info["k1"]))
+    nd = W_trg.shape[0]
+    if G_src is None or G_src.shape != (nd, Ns * info["k0"]):
+        G_src = np.zeros((nd, Ns * info["k0"]), dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    _check(lib().sctl_amd_eval_transpose_densities_host(info["id"], real, nd, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                                        _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(W_trg, dt, nd * Nt * info["k1"], "W_trg"),
+                                                        _np_ptr(G_src, dt, nd * Ns * info["k0"], "G_src"), 1 if accumulate else 0, digits, cp, cb, device),
+           "eval_transpose_densities_host")
+    return G_src
+
+
+def eval_transpose_densities_device(name, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_transpose_densities_device), enqueued on `stream` (default: torch's current stream);
+    W_trg of shape (nd, Nt*TrgDim), G_src (nd, Ns*SrcDim) accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    if W_trg.dim() != 2 or W_trg.shape[1] != Nt * info["k1"]:
+        raise SctlAmdError("W_trg must have shape (nd, %d)" % (Nt * info["k1"]))
+    nd = W_trg.shape[0]
+    if G_src is None or tuple(G_src.shape) != (nd, Ns * info["k0"]):
+        G_src = torch.zeros((nd, Ns * info["k0"]), dtype=tdt, device=r_trg.device)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_transpose_densities_device(info["id"], real, nd, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                                              _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(W_trg, tdt, nd * Nt * info["k1"], "W_trg"),
+                                                              _t_ptr(G_src, tdt, nd * Ns * info["k0"], "G_src"), digits, cp, cb, C.c_void_p(st.cuda_stream)),
+               "eval_transpose_densities_device")
+    return G_src
+
+
 def _grad_wanted(info, want):
     if want is None:
         want = ("trg", "src", "nrm") if info["nd"] else ("trg", "src")
@@ -581,6 +641,11 @@ class GenericKernel:
         if isinstance(r_trg, np.ndarray):
             return eval_transpose_host(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
         return eval_transpose_device(self._info["id"], r_trg, r_src, n_src, w_trg, g_src, digits, self._ctx, **kw)
+
+    def EvalTransposeDensities(self, G_src, r_trg, r_src, n_src, W_trg, digits=-1, **kw):
+        if isinstance(r_trg, np.ndarray):
+            return eval_transpose_densities_host(self._info["id"], r_trg, r_src, n_src, W_trg, G_src, digits, self._ctx, **kw)
+        return eval_transpose_densities_device(self._info["id"], r_trg, r_src, n_src, W_trg, G_src, digits, self._ctx, **kw)
 
     def EvalGrad(self, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
         if isinstance(r_trg, np.ndarray):

@@ -11,6 +11,12 @@ of r_trg, r_src, n_src need a gradient.
     u = sctl_amd.autograd.kernel_sum_geometry("Laplace3D-DxU", r_trg, r_src, n_src, v_src)   # any of the four may require grad
     u.square().sum().backward()                                                               # r_trg.grad, r_src.grad, n_src.grad, v_src.grad
 
+kernel_sum_densities is kernel_sum for several densities on one geometry: the forward is sctl_amd_eval_densities_device, the backward
+sctl_amd_eval_transpose_densities_device, A^T (dloss/dU) for all rows in one pass; densities only.
+
+    U = sctl_amd.autograd.kernel_sum_densities("Stokes3D-FxUP", r_trg, r_src, None, V_src)    # V_src of shape (nd, Ns*SrcDim); U (nd, Nt*TrgDim)
+    U.square().sum().backward()                                                      # V_src.grad[m] = A^T (2 U[m])
+
 lists_sum is kernel_sum over the P2P lists of a ListsPlan made with directions="both": the forward is plan.eval_device, the backward
 plan.eval_transpose_device; densities only.
 
@@ -55,6 +61,35 @@ def kernel_sum(name, r_trg, r_src, n_src, v_src, digits=-1, ctx=None):
             raise api.SctlAmdError("kernel_sum differentiates with respect to the densities only: %s requires grad; kernel_sum_geometry differentiates "
                                    "coordinates and normals too" % what)
     return _KernelSum.apply(name, r_trg, r_src, n_src, v_src, digits, ctx)
+
+
+class _KernelSumDensities(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, name, r_trg, r_src, n_src, V_src, digits, ctx):
+        fn_ctx.kernel = (name, digits, ctx)
+        fn_ctx.save_for_backward(r_trg, r_src, n_src)
+        return api.eval_densities_device(name, r_trg.detach(), r_src.detach(), None if n_src is None else n_src.detach(), V_src.detach().contiguous(), digits=digits, ctx=ctx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_U):
+        name, digits, ctx = fn_ctx.kernel
+        r_trg, r_src, n_src = fn_ctx.saved_tensors
+        G = None
+        if fn_ctx.needs_input_grad[4]:
+            G = api.eval_transpose_densities_device(name, r_trg, r_src, n_src, grad_U.contiguous(), digits=digits, ctx=ctx)
+        return None, None, None, None, G, None, None
+
+
+def kernel_sum_densities(name, r_trg, r_src, n_src, V_src, digits=-1, ctx=None):
+    """sctl_amd.eval_densities_device on torch CUDA tensors (a fresh result of shape (nd, Nt*TrgDim)) that autograd can differentiate with respect to
+    V_src, of shape (nd, Ns*SrcDim): the backward is eval_transpose_densities_device on the forward's stream, as autograd arranges, and is
+    once-differentiable."""
+    for what, t in (("r_trg", r_trg), ("r_src", r_src), ("n_src", n_src)):
+        if t is not None and t.requires_grad:
+            raise api.SctlAmdError("kernel_sum_densities differentiates with respect to the densities only: %s requires grad; kernel_sum_geometry "
+                                   "differentiates coordinates and normals too" % what)
+    return _KernelSumDensities.apply(name, r_trg, r_src, n_src, V_src, digits, ctx)
 
 
 class _KernelSumGeometry(torch.autograd.Function):

@@ -1,6 +1,7 @@
 // C ABI of libsctl_amd.so (include/sctl_amd.h): the kernel registry and plugin loading, the error text, the shared argument checks, init / finalize,
 // the info and plan queries, and the device-pointer entries (checks + one driver call of eval_drivers.hpp).  The host-buffer entries are in
-// host_entries.hip, the operator handle in op.hip.  All arithmetic lives in eval_kernel.hpp / multi_kernel.hpp / ukernels.hpp.
+// host_entries.hip, the operator handle in op.hip.  All arithmetic lives in eval_kernel.hpp / multi_kernel.hpp /
+// multi_transpose_kernel.hpp / ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -131,6 +132,15 @@ int check_transpose(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, cons
   const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
   if (rc) return rc;
   if ((Nt > 0 && !w_trg) || (Ns > 0 && !g_src)) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or result array");
+  if (!has_transpose(*k)) return no_transpose(*k);
+  return SCTL_AMD_OK;
+}
+int check_transpose_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                              const void* w_trg, const void* g_src, int ctx_bytes, const void* ctx) {
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of weight vectors");
+  const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd > 0 && ((Nt > 0 && !w_trg) || (Ns > 0 && !g_src))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or result array");
   if (!has_transpose(*k)) return no_transpose(*k);
   return SCTL_AMD_OK;
 }
@@ -354,6 +364,62 @@ int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, i
   if (src_per_lane) *src_per_lane = kTTvalues[p.t_idx];
   if (splits) *splits = p.splits;
   if (workspace_bytes) *workspace_bytes = p.workspace_bytes;
+  return SCTL_AMD_OK;
+}
+
+// ---- several weight vectors through the transposed sum: g_src[m] += A^T w_trg[m] ------------------------------------------------------------
+// nd == 1 goes through the single transposed entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+int sctl_amd_eval_transpose_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                             const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_transpose_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_transpose_device(kernel, real, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes, stream);
+  if (device_count_quiet() <= 0) return no_device();
+  return eval_transpose_densities_device(*k, real, nd, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_transpose_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* vectors_per_pass, int* passes,
+                                           int* src_per_lane, int* splits, int64_t* workgroups, int64_t* workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (const int rc = check_real_sizes(k, real, Nt, Ns)) return rc;
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of weight vectors");
+  if (!has_transpose(*k)) return no_transpose(*k);
+  (void)digits;   // every accuracy mode runs the same launch geometry
+  int vpp = 0, np = 0, t = 0, s = 0;
+  int64_t wg = 0, ws = 0;
+  const MultiTEntry* me = multi_t_entry(k->id);
+  if (nd == 1 || (nd > 1 && !me)) {   // the single transposed plan, once per weight vector
+    const PlanT p = make_plan_t(*k, real, Nt, Ns);
+    const int64_t group = (int64_t)kBlock * kTTvalues[p.t_idx];
+    vpp = 1; np = nd; t = kTTvalues[p.t_idx]; s = p.splits; ws = p.workspace_bytes;
+    for (int64_t s0 = 0; s0 < Ns; s0 += p.owners_per_launch) {
+      const int64_t n = (Ns - s0 < p.owners_per_launch) ? Ns - s0 : p.owners_per_launch;
+      wg += (n + group - 1) / group * p.splits;
+    }
+  } else if (nd > 1) {
+    // the first pass is the widest; the workspace is the largest any pass asks for
+    for (int m0 = 0; m0 < nd;) {
+      const int left = nd - m0;
+      const MultiTPlan p = make_plan_multi_t(*k, *me, multi_t_form(*me, left), real, Nt, Ns > 0 ? Ns : 1);
+      if (np == 0) {
+        vpp = p.M; t = p.T; s = p.splits;
+        for (int64_t s0 = 0; s0 < Ns; s0 += p.ns_launch) {   // workgroups of all source launches of the pass
+          const int64_t n = (Ns - s0 < p.ns_launch) ? Ns - s0 : p.ns_launch;
+          wg += (n + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T) * p.splits;
+        }
+      }
+      ws = p.workspace_bytes > ws ? p.workspace_bytes : ws;
+      np++;
+      m0 += left < p.M ? left : p.M;
+    }
+  }
+  if (vectors_per_pass) *vectors_per_pass = vpp;
+  if (passes) *passes = np;
+  if (src_per_lane) *src_per_lane = t;
+  if (splits) *splits = s;
+  if (workgroups) *workgroups = wg;
+  if (workspace_bytes) *workspace_bytes = ws;
   return SCTL_AMD_OK;
 }
 

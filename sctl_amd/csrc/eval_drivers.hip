@@ -1,5 +1,6 @@
 // Launch planning and the typed launch drivers of the all-pairs evaluators, behind the untyped functions of eval_drivers.hpp: the forward sum, several
-// densities, the transposed sum, the geometry gradients and the kernel matrix.  All arithmetic lives in eval_kernel.hpp / multi_kernel.hpp / ukernels.hpp.
+// densities, the transposed sum, several weight vectors through it, the geometry gradients and the kernel matrix.  All arithmetic lives in eval_kernel.hpp /
+// multi_kernel.hpp / multi_transpose_kernel.hpp / ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -433,6 +434,115 @@ int eval_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, 
 }
 }  // namespace
 
+// ---- several weight vectors through the transposed sum (sctl_amd_eval_transpose_densities_*, multi_transpose_kernel.hpp) -----------------
+const MultiTEntry* multi_t_entry(int kernel_id) {
+  static const MultiTEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &multi_t_Laplace3D_FxU(), &multi_t_Laplace3D_DxU(), &multi_t_Laplace3D_FxdU(),  &multi_t_Stokes3D_FxU(),      &multi_t_Stokes3D_DxU(),
+      &multi_t_Stokes3D_FxT(),  &multi_t_Stokes3D_FSxU(), &multi_t_Stokes3D_FxUP(), &multi_t_Laplace3D_FDxUdU(), &multi_t_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+int multi_t_form(const MultiTEntry& me, int left) {
+  for (int i = 0; i < kNumMultiTM; i++)
+    if (me.t[i] && (kMultiTM[i] >= left || kMultiTM[i] == me.m_max)) return i;
+  return 0;
+}
+
+MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int form, int real, int64_t Nt, int64_t Ns) {
+  MultiTPlan p{};
+  p.form = form; p.M = kMultiTM[form]; p.T = me.t[form];
+  const int64_t rs = (int64_t)real_size(real), per_wg = (int64_t)kBlock * p.T;
+  const int64_t ntile = (Nt + kTile - 1) / kTile;
+  const int64_t cap = transpose_workspace_cap();
+  int64_t l2 = 1;
+  if ((double)Nt * (double)Ns >= 17179869184.0) {   // one split's streamed data, all M weight vectors of a target with it, <= 2 MB
+    const int64_t trg_bytes = Nt * (3 + (int64_t)p.M * k.k1) * rs;
+    l2 = (trg_bytes + (2 << 20) - 1) / (2 << 20);
+    l2 = (l2 + 7) / 8 * 8;
+    if (l2 > 64) l2 = 64;
+  }
+  auto geometry = [&](int64_t ns) {
+    p.ns_launch = ns;
+    p.wg_x = (ns + per_wg - 1) / per_wg;
+    const int64_t want = (int64_t)cu_count() * ((double)ns * (double)Nt < 2147483648.0 ? 4 : 8);
+    int64_t s = (want + p.wg_x - 1) / p.wg_x;
+    if (s > 1024) s = 1024;
+    if (s < l2) s = l2;
+    if (s > ntile) s = ntile;
+    if (s < 1) s = 1;
+    const int64_t tiles_per = (ntile + s - 1) / s;
+    p.chunk = (tiles_per > 0 ? tiles_per : 1) * kTile;
+    int64_t splits = (Nt + p.chunk - 1) / p.chunk;
+    if (splits >= 8) splits = (splits + 7) / 8 * 8;   // (the splits past the targets have no work)
+    p.splits = (int)(splits < 1 ? 1 : splits);
+    p.workspace_bytes = p.splits > 1 ? (int64_t)p.M * p.splits * ns * k.k0 * rs : 0;
+  };
+  p.launches = 1;
+  for (;;) {
+    int64_t ns = (Ns + p.launches - 1) / p.launches;
+    ns = (ns + per_wg - 1) / per_wg * per_wg;
+    if (ns > Ns) ns = Ns;
+    geometry(ns);
+    if (p.workspace_bytes <= cap || ns <= per_wg) break;
+    const int64_t more = (p.workspace_bytes + cap - 1) / cap * p.launches;   // (at least one more launch)
+    p.launches = more > p.launches ? more : p.launches + 1;
+  }
+  p.launches = (Ns + p.ns_launch - 1) / p.ns_launch;
+  return p;
+}
+
+namespace {
+// nd >= 2 weight vectors, row-major, on the device: passes of the widest form, the last pass on the narrowest form that takes what is left, as
+// eval_densities_device_t.  g is accumulated into.  A plugin kernel with pair_t has no pair_tm: its rows go one at a time through the single path.
+template <class R>
+int eval_transpose_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* w, R* g,
+                                      int digits, const void* ctx, hipStream_t st) {
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  const int64_t w_stride = Nt * k.k1, g_stride = Ns * k.k0;
+  const MultiTEntry* me = multi_t_entry(k.id);
+  const int mode = mode_for(real, digits);
+  for (int m0 = 0; m0 < nd;) {
+    const int left = nd - m0;
+    if (!me) {
+      const int rc = eval_transpose_device_t<R>(k, real, Nt, Ns, xt, xs, xn, w + m0 * w_stride, g + m0 * g_stride, digits, ctx, st);
+      if (rc) return rc;
+      m0++;
+      continue;
+    }
+    (void)hipGetLastError();
+    const MultiTPlan p = make_plan_multi_t(k, *me, multi_t_form(*me, left), real, Nt, Ns);
+    const int nact = left < p.M ? left : p.M;
+    MultiTArgs<R> a{};
+    a.Nt = Nt; a.xt = xt; a.w = w + m0 * w_stride; a.w_stride = w_stride; a.g_stride = g_stride;
+    a.chunk = p.chunk; a.nact = nact; a.scale = (R)(k.scale / k.acc_factor[mode]); a.ctx = make_ctx(k, ctx);
+    if (p.splits > 1) {
+      void* ws = nullptr;
+      HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+      a.partial = (R*)ws;
+    }
+    MultiTLaunch<R> launch;
+    if constexpr (std::is_same<R, double>::value) launch = me->f64[mode][p.form];
+    else launch = me->f32[mode][p.form];
+    for (int64_t s0 = 0; s0 < Ns; s0 += p.ns_launch) {   // one launch unless the partial sums of all owners would pass the bound
+      const int64_t ns = (Ns - s0 < p.ns_launch) ? Ns - s0 : p.ns_launch;
+      a.Ns = ns; a.xs = xs + s0 * 3; a.xn = xn ? xn + s0 * k.nd : nullptr; a.g_src = g + m0 * g_stride + s0 * k.k0;
+      const dim3 grid((unsigned)((ns + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T)), (unsigned)p.splits);
+      launch(a, grid, st);
+      HIP_TRY(hipGetLastError());
+      if (p.splits > 1) {
+        const int64_t n = ns * k.k0;
+        for (int m = 0; m < nact; m++)
+          hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.g_src + m * g_stride,
+                             (const R*)(a.partial + (int64_t)m * p.splits * n), n, p.splits, a.scale);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    count_work((int64_t)nact * Nt * Ns, k);
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+}  // namespace
+
 // ---- the untyped seam: `real` picks the template here and nowhere else ----------------------------------------------------------------------------
 int eval_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, void* v, int digits,
                 const void* ctx, hipStream_t st, int64_t nt_whole, bool presorted) {
@@ -445,6 +555,10 @@ int eval_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, in
 int eval_transpose_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* w, void* g,
                           int digits, const void* ctx, hipStream_t st) {
   return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_transpose_device_t<R>(k, real, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)w, (R*)g, digits, ctx, st); });
+}
+int eval_transpose_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* w,
+                                    void* g, int digits, const void* ctx, hipStream_t st) {
+  return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_transpose_densities_device_t<R>(k, real, nd, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)w, (R*)g, digits, ctx, st); });
 }
 int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* w,
                      void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st) {

@@ -3,6 +3,7 @@
 #pragma once
 #include "internal.hpp"
 #include "multi_kernel.hpp"
+#include "multi_transpose_kernel.hpp"
 
 namespace sctl_amd {
 // centered.hip
@@ -58,6 +59,18 @@ struct MultiPlan {
 };
 MultiPlan make_plan_multi(const KernelEntry& k, const MultiEntry& me, int form, int real, int64_t Nt, int64_t Ns);
 
+// ---- several weight vectors through the transposed sum (multi_transpose_kernel.hpp) ----
+const MultiTEntry* multi_t_entry(int kernel_id);    // null for a registered plugin kernel: its rows go one at a time through the single transposed path
+int multi_t_form(const MultiTEntry& me, int left);  // as multi_form
+// make_plan_multi with the point sets exchanged: the SOURCES own the sums and tile grid.x, the TARGET range is split; the L2 rule counts all M weight
+// vectors in a split's streamed bytes, the splits come in eights from 8 on, and the partial sums [M][splits][ns_launch * K0] stay within 2 GB (or what
+// SCTL_AMD_TRANSPOSE_WORKSPACE lowers that to) by cutting the owners into launches of whole workgroups, never by taking fewer splits.
+struct MultiTPlan {
+  int form, M, T, splits;
+  int64_t chunk, ns_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the sources of one launch of ns_launch sources
+};
+MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int form, int real, int64_t Nt, int64_t Ns);
+
 // ---- the tile-centred fast path (centered.hip) ----
 // mode < 0: the mode of the default accuracy request (what an operator handle sorts its targets for)
 bool has_centered_path(const KernelEntry& k, int real, int mode = -1);
@@ -80,6 +93,9 @@ int eval_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, in
 // g[s,k0] += scale * sum_t sum_k1 U(x_t - x_s, n_s)[k0][k1] w[t,k1]
 int eval_transpose_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* w, void* g,
                           int digits, const void* ctx, hipStream_t st);
+// nd >= 2 weight vectors, row-major: g[m] += A^T w[m] (a single row must take eval_transpose_device: this one would run it on the form of 2)
+int eval_transpose_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* w,
+                                    void* g, int digits, const void* ctx, hipStream_t st);
 // g_trg, g_src, g_nrm += the gradients of <w, A f> with respect to the target coordinates, the source coordinates and the source normals; a null output is
 // not computed, and a side whose outputs are all null is not launched
 int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* w,

@@ -205,6 +205,28 @@ int sctl_amd_eval_transpose_host(int kernel, int real, int64_t Nt, int64_t Ns, c
   return rc ? rc : c.finish();
 }
 
+// nd == 1 goes through the single transposed entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+// Coordinates and normals go down once, the nd weight rows in one transfer, the nd result rows come back in one.
+int sctl_amd_eval_transpose_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                           const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes, int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_transpose_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_transpose_host(kernel, real, Nt, Ns, r_trg, r_src, n_src, w_trg, g_src, accumulate, digits, ctx, ctx_bytes, device);
+  if ((rc = check_device(device))) return rc;
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;   // nothing is read or written
+  const size_t rs = real_size(real);
+  HostCall c(device, real);
+  c.in(0, r_trg, (size_t)Nt * 3 * rs);
+  c.in(1, r_src, (size_t)Ns * 3 * rs);
+  c.in(2, n_src, (size_t)Ns * k->nd * rs);
+  c.in(3, w_trg, (size_t)nd * Nt * k->k1 * rs);
+  c.out(4, g_src, (size_t)nd * Ns * k->k0 * rs, HostCall::kZero | HostCall::kStaged | (accumulate ? HostCall::kAccumulate : 0));
+  rc = c.start();
+  if (rc == SCTL_AMD_OK) rc = eval_transpose_densities_device(*k, real, nd, Nt, Ns, c.dev(0), c.dev(1), c.dev(2), c.dev(3), c.dev(4), digits, ctx, c.st);
+  return rc ? rc : c.finish();
+}
+
 int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
                             const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int accumulate, int digits, const void* ctx, int ctx_bytes, int device) {
   const KernelEntry* k = registry(kernel);

@@ -1,0 +1,8 @@
+// Transposed forms of Laplace3D_FDxUdU for several weight vectors (multi_transpose_kernel.hpp): sources per lane 2 / 1 / 1 for 2 / 4 / 8 weight vectors.
+#include "multi_transpose_kernel.hpp"
+namespace sctl_amd {
+const MultiTEntry& multi_t_Laplace3D_FDxUdU() {
+  static const MultiTEntry e = make_multi_t_entry<Laplace3D_FDxUdU, 2, 1, 1>();
+  return e;
+}
+}  // namespace sctl_amd
