@@ -245,8 +245,8 @@ int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, i
  * weight vectors per pass (4 for the traction kernel) on the exact all-pairs kernel (csrc/multi_transpose_kernel.hpp): sums in a fixed
  * order, bit-reproducible; a registered kernel with pair_t (which has no several-vectors form) is evaluated one row at a time on the same
  * stream, one without pair_t is SCTL_AMD_ERR_UNKNOWN_KERNEL.  fp32 runs this exact pair at every `digits`, as the single transposed entry
- * does.  Counters grow by nd*Nt*Ns pairs.  Not provided: several weight vectors for sctl_amd_near_apply_transpose_*,
- * sctl_amd_op_eval_transpose / _potential_transpose and the P2P lists, and any multi-GPU form. */
+ * does.  Counters grow by nd*Nt*Ns pairs.  Not provided: several weight vectors over the P2P lists and any
+ * multi-GPU form (the near field and the operator handle have theirs: sctl_amd_near_apply_transpose_densities_*). */
 /* DEVICE arrays; enqueued on `stream`; g_src is accumulated into. */
 int sctl_amd_eval_transpose_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                                              const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream);
@@ -386,7 +386,7 @@ int sctl_amd_op_eval_potential_densities(sctl_amd_op* op, int nd, const void* v_
  * device arrays (its work list, the gathered W) is allocated on the first transposed call, not by sctl_amd_near_create.  That first call
  * therefore allocates and copies the work list synchronously before it enqueues (it cannot be captured into a graph); later calls only enqueue.  Null handle
  * or arrays: SCTL_AMD_ERR_BAD_ARGUMENT before any device work; an operator without entries returns SCTL_AMD_OK and touches nothing.
- * Several weight vectors per call are NOT provided in the transposed direction: call once per vector. */
+ * Several weight vectors per call: sctl_amd_near_apply_transpose_densities_* below. */
 int sctl_amd_near_apply_transpose_host(sctl_amd_near* op, const void* W, void* G);                   /* HOST arrays, G accumulated into            */
 int sctl_amd_near_apply_transpose_device(sctl_amd_near* op, const void* W, void* G, void* stream);   /* DEVICE arrays, enqueue, G accumulated into */
 /* The adjoint of sctl_amd_op_eval (g_src = D_w A^T C_n^T w) and of sctl_amd_op_eval_potential (that, and g_near = N^T w) on the
@@ -401,6 +401,35 @@ int sctl_amd_near_apply_transpose_device(sctl_amd_near* op, const void* W, void*
 int sctl_amd_op_eval_transpose(sctl_amd_op* op, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes);
 int sctl_amd_op_eval_potential_transpose(sctl_amd_op* op, const void* w_trg, void* g_src_far, void* g_near, int accumulate, int digits,
                                          const void* ctx, int ctx_bytes);
+
+/* ---- several weight vectors through the adjoint of the near field and of ComputePotential ----------------------------------------- */
+/* G[m] += N^T W[m] for nd weight vectors against one near-field operator, every entry of K_near read from HBM ONCE per pass instead of
+ * once per vector, a target's scatter indices read once for all rows of the gather.  Row-major, the layouts of
+ * sctl_amd_near_apply_densities_*: W[nd][Ntrg*trg_dim], G[nd][density_len]; row m is what sctl_amd_near_apply_transpose_* takes and
+ * returns, and every row of G is ACCUMULATED into.  nd == 1 IS the single-vector entry (bit-identical), nd == 0 does nothing, nd < 0 is
+ * SCTL_AMD_ERR_BAD_ARGUMENT; null handle or arrays are reported as the single entries report them, before any device work.  Any nd is
+ * legal: fp64 runs passes of 4 vectors and a last pass of the narrower form (2 or 4) that takes what is left, fp32 passes of 2 (its form
+ * of 4 measured slower than four single calls; a form of 8 does not fit the registers), one vector left over going through the
+ * single-vector kernels.  The sums use the single-vector kernel's order of additions in a lane and its tree
+ * across lanes (no atomics): results are bit-identical from run to run and between the host and the device entry.  Entries of G that
+ * belong to elements without a matrix or without near targets keep their bits in every row.  The gathered weights of a pass,
+ * M * near_entries * trg_dim values for the widest pass M the handle has run, belong to the handle; they are allocated and zero-filled
+ * on the first several-vectors call (on the caller's stream) and grow with the widest pass.  If they cannot be allocated the call
+ * returns SCTL_AMD_ERR_HIP and the handle stays usable.  The host entry keeps nd * (density_len + Ntrg*trg_dim) values of device and
+ * pinned staging memory, shared with sctl_amd_near_apply_densities_host.  Not provided: the P2P lists and rank-parallel forms. */
+int sctl_amd_near_apply_transpose_densities_host(sctl_amd_near* op, int nd, const void* W, void* G);                   /* HOST arrays            */
+int sctl_amd_near_apply_transpose_densities_device(sctl_amd_near* op, int nd, const void* W, void* G, void* stream);   /* DEVICE arrays, enqueue */
+/* sctl_amd_op_eval_transpose / _potential_transpose for nd weight vectors, HOST arrays w_trg[nd][Nt*TrgDim] (Nt*TrgDim/3 with target
+ * normals), g_src / g_src_far[nd][Ns*SrcDim], g_near[nd][sum(elem_nds_cnt)*SrcDim]: on every device the slab of every row of w goes
+ * down once, the normals expand every row, the far leg runs as sctl_amd_eval_transpose_densities_device does (its pass widths per
+ * kernel and precision), the weights scale every row, the near sub-operator takes all rows through
+ * sctl_amd_near_apply_transpose_densities_device on the same stream, and the results come up once; the host adds the devices' partial
+ * results in device order, row by row.  Errors as the single entries; nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing after
+ * the argument checks, nd == 1 runs exactly what the single entries run.  The counters grow by nd*Nt*Ns. */
+int sctl_amd_op_eval_transpose_densities(sctl_amd_op* op, int nd, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx,
+                                         int ctx_bytes);
+int sctl_amd_op_eval_potential_transpose_densities(sctl_amd_op* op, int nd, const void* w_trg, void* g_src_far, void* g_near, int accumulate,
+                                                   int digits, const void* ctx, int ctx_bytes);
 
 int sctl_amd_near_info(const sctl_amd_near* op, int64_t* density_len, int64_t* potential_len, int64_t* near_entries,
                        int64_t* operator_bytes, int64_t* workgroups);

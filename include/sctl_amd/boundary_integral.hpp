@@ -366,7 +366,82 @@ template <class Real, class Kernel> class BoundaryIntegralOp {
     ScatterFarFieldGradient(G, G_far);
   }
 
+  // ---- the adjoint for several weight vectors (block BiCG / QMR / LSQR, adjoint solves with several right-hand sides): W is nd x Dim(1), G nd x Dim(0),
+  // row m what the single transposed entry takes and returns.  The weights go to the devices once and every operator entry of the near field is read
+  // once per pass (sctl_amd_op_eval_transpose_densities, sctl_amd_near_apply_transpose_densities_host, sctl_amd_op_eval_potential_transpose_densities);
+  // the far part of every row is mapped back by FarFieldDensityOperatorTranspose on the host. ----
+  void ComputeFarFieldTransposeDensities(Matrix<Real>& G, const Matrix<Real>& W) const {
+    SetupBasic();
+    SetupFar();
+    const Long nd = W.Dim(0), Nsrc = X_far.Dim() / COORD_DIM, Ntrg = Xtrg.Dim() / COORD_DIM;
+    SCTL_AMD_ASSERT(nd == 0 || W.Dim(1) == Dim(1));
+    if (G.Dim(0) != nd || G.Dim(1) != Dim(0)) G.ReInit(nd, Dim(0));
+    G.SetZero();
+    if (!nd || !Ntrg || !Nsrc) return;
+    Matrix<Real> G_far(nd, Nsrc * KDIM0);
+    CheckStatus(sctl_amd_op_eval_transpose_densities(far_op, (int)nd, W.begin(), G_far.begin(), /*accumulate*/ 0, fmm_digits(), ker_.GetCtxPtr(),
+                                                     (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_transpose_densities");
+    ScatterFarFieldGradientRows(G, G_far);
+  }
+
+  // every row of G is ACCUMULATED into when G has the right shape
+  void ComputeNearInteracTransposeDensities(Matrix<Real>& G, const Matrix<Real>& W) const {
+    RefuseMatrixFree("ComputeNearInteracTransposeDensities");
+    Setup();
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long nd = W.Dim(0), Ntrg = Xtrg.Dim() / COORD_DIM, Nelem = near_elem_cnt.Dim();
+    SCTL_AMD_ASSERT(nd == 0 || W.Dim(1) == Dim(1));
+    if (G.Dim(0) != nd || G.Dim(1) != Dim(0)) {
+      G.ReInit(nd, Dim(0));
+      G.SetZero();
+    }
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near || !nd) return;
+    if (!near_op) {
+      const int rc = sctl_amd_near_create(RealTag<Real>::value, DeviceSet::Get()[0], Nelem, (int)KDIM0, (int)KDIM1_, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt),
+                                          PtrOf(K_near_cnt), K_near.Dim() ? (const void*)K_near.begin() : nullptr, Ntrg, PtrOf(near_scatter_index),
+                                          PtrOf(near_trg_cnt), PtrOf(near_trg_dsp), &near_op);
+      CheckStatus(rc, "sctl_amd_near_create");
+    }
+    CheckStatus(sctl_amd_near_apply_transpose_densities_host(near_op, (int)nd, W.begin(), G.begin()), "sctl_amd_near_apply_transpose_densities_host");
+  }
+
+  void ComputePotentialTransposeDensities(Matrix<Real>& G, const Matrix<Real>& W) const {
+    RefuseMatrixFree("ComputePotentialTransposeDensities");
+    Setup();
+    const Long nd = W.Dim(0), Nelem = near_elem_cnt.Dim();
+    const Long N_near = (Nelem ? near_elem_dsp[Nelem - 1] + near_elem_cnt[Nelem - 1] : 0);
+    if (!N_near || !far_op || !nd) {   // as ComputePotentialTranspose: the two legs as they are
+      ComputeFarFieldTransposeDensities(G, W);
+      ComputeNearInteracTransposeDensities(G, W);
+      return;
+    }
+    const Integer KDIM1_ = (trg_normal_dot_prod_ ? KDIM1 / COORD_DIM : KDIM1);
+    const Long Nsrc = X_far.Dim() / COORD_DIM;
+    SCTL_AMD_ASSERT(W.Dim(1) == Dim(1));
+    if (G.Dim(0) != nd || G.Dim(1) != Dim(0)) G.ReInit(nd, Dim(0));
+    if (!near_attached) {
+      CheckStatus(sctl_amd_op_set_near(far_op, (int)KDIM0, (int)KDIM1_, Nelem, PtrOf(elem_nds_cnt), PtrOf(near_elem_cnt), PtrOf(K_near_cnt),
+                                       K_near.Dim() ? (const void*)K_near.begin() : nullptr, PtrOf(near_scatter_index), PtrOf(near_trg_cnt), PtrOf(near_trg_dsp)),
+                  "sctl_amd_op_set_near");
+      near_attached = true;
+    }
+    Matrix<Real> G_far(nd, Nsrc * KDIM0);
+    CheckStatus(sctl_amd_op_eval_potential_transpose_densities(far_op, (int)nd, W.begin(), G_far.begin(), G.begin(), /*accumulate*/ 0, fmm_digits(),
+                                                               ker_.GetCtxPtr(), (int)Kernel::CTX_BYTES),
+                "sctl_amd_op_eval_potential_transpose_densities");
+    ScatterFarFieldGradientRows(G, G_far);
+  }
+
  private:
+  void ScatterFarFieldGradientRows(Matrix<Real>& G, Matrix<Real>& G_far) const {
+    for (Long m = 0; m < G.Dim(0); m++) {
+      Vector<Real> g(G.Dim(1), G[m], false), g_far(G_far.Dim(1), G_far[m], false);
+      ScatterFarFieldGradient(g, g_far);
+    }
+  }
+
   void RefuseMatrixFree(const char* what) const {
     for (const auto& it : elem_lst_map)
       if (it.second->MatrixFree())

@@ -36,7 +36,9 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_lists_transpose_host",
            "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan",
            "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose",
-           "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan"]
+           "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan",
+           "sctl_amd_near_apply_transpose_densities_host", "sctl_amd_near_apply_transpose_densities_device", "sctl_amd_op_eval_transpose_densities",
+           "sctl_amd_op_eval_potential_transpose_densities"]
 
 
 class SctlAmdError(RuntimeError):
@@ -153,6 +155,10 @@ def lib():
     L.sctl_amd_near_apply_transpose_device.argtypes = [vp, vp, vp, vp]
     L.sctl_amd_op_eval_transpose.argtypes = [vp, vp, vp, ci, ci, vp, ci]
     L.sctl_amd_op_eval_potential_transpose.argtypes = [vp, vp, vp, vp, ci, ci, vp, ci]
+    L.sctl_amd_near_apply_transpose_densities_host.argtypes = [vp, ci, vp, vp]
+    L.sctl_amd_near_apply_transpose_densities_device.argtypes = [vp, ci, vp, vp, vp]
+    L.sctl_amd_op_eval_transpose_densities.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sctl_amd_op_eval_potential_transpose_densities.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, ci]
     _LIB = L
     return L
 
@@ -788,6 +794,45 @@ class DirectOp:
                                                           1 if accumulate else 0, digits, cp, cb), "op_eval_potential_transpose")
         return g_src_far, g_near
 
+    def _out2(self, a, nd, n, what):
+        if a is None:
+            return np.zeros((nd, n), dtype=self.dtype)
+        if not isinstance(a, np.ndarray) or a.shape != (nd, n) or a.dtype != self.dtype or not a.flags.c_contiguous:
+            raise SctlAmdError("%s must be a contiguous %s array of shape (%d, %d)" % (what, self.dtype, nd, n))
+        return a
+
+    def eval_transpose_densities(self, W_trg, G_src=None, accumulate=False, digits=-1):
+        """eval_transpose() for nd weight vectors in one pass over the devices (sctl_amd_op_eval_transpose_densities): W_trg of shape
+        (nd, Nt*k1) with k1 = TrgDim, or TrgDim/3 with target normals; returns G_src of shape (nd, Ns*SrcDim)."""
+        k1 = self.info["k1"] // 3 if getattr(self, "_dot", False) else self.info["k1"]
+        if np.ndim(W_trg) != 2 or np.shape(W_trg)[1] != self.Nt * k1:
+            raise SctlAmdError("W_trg must have shape (nd, %d)" % (self.Nt * k1))
+        nd = np.shape(W_trg)[0]
+        G_src = self._out2(G_src, nd, self.Ns * self.info["k0"], "G_src")
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_transpose_densities(self._h, nd, _np_ptr(W_trg, self.dtype, nd * self.Nt * k1, "W_trg"),
+                                                          _np_ptr(G_src, self.dtype, G_src.size, "G_src"), 1 if accumulate else 0, digits, cp, cb),
+               "op_eval_transpose_densities")
+        return G_src
+
+    def eval_potential_transpose_densities(self, W_trg, G_src_far=None, G_near=None, accumulate=False, digits=-1):
+        """eval_potential_transpose() for nd weight vectors in one pass over the devices (sctl_amd_op_eval_potential_transpose_densities):
+        W_trg of shape (nd, Nt*trg_dim); returns (G_src_far, G_near) of shapes (nd, Ns*SrcDim) and (nd, near density length)."""
+        if not hasattr(self, "_near_k1"):
+            raise SctlAmdError("no near-field operator attached: call set_near first")
+        k1 = self._near_k1
+        if np.ndim(W_trg) != 2 or np.shape(W_trg)[1] != self.Nt * k1:
+            raise SctlAmdError("W_trg must have shape (nd, %d)" % (self.Nt * k1))
+        nd = np.shape(W_trg)[0]
+        G_src_far = self._out2(G_src_far, nd, self.Ns * self.info["k0"], "G_src_far")
+        G_near = self._out2(G_near, nd, self._near_len, "G_near")
+        keep, cp, cb = _ctx_blob(self.info, self.ctx)
+        _check(lib().sctl_amd_op_eval_potential_transpose_densities(self._h, nd, _np_ptr(W_trg, self.dtype, nd * self.Nt * k1, "W_trg"),
+                                                                    _np_ptr(G_src_far, self.dtype, G_src_far.size, "G_src_far"),
+                                                                    _np_ptr(G_near, self.dtype, G_near.size, "G_near"), 1 if accumulate else 0, digits, cp, cb),
+               "op_eval_potential_transpose_densities")
+        return G_src_far, G_near
+
     def close(self):
         if self._h:
             lib().sctl_amd_op_destroy(self._h)
@@ -896,6 +941,38 @@ class NearOp:
             _check(lib().sctl_amd_near_apply_densities_device(self._h, nd, _t_ptr(F, tdt, nd * self.density_len, "F"), _t_ptr(U, tdt, nd * self.potential_len, "U"),
                                                               C.c_void_p(st.cuda_stream)), "near_apply_densities_device")
         return U
+
+    def apply_transpose_densities(self, W, G=None):
+        """apply_transpose() for nd weight vectors with the operator read once per pass (sctl_amd_near_apply_transpose_densities_host): W of
+        shape (nd, potential_len); every row of G (nd, density_len) is accumulated into, G=None starts from zero."""
+        W = np.ascontiguousarray(W, dtype=self.dtype)
+        if W.ndim != 2 or W.shape[1] != self.potential_len:
+            raise SctlAmdError("weights must have shape (nd, %d)" % self.potential_len)
+        nd = W.shape[0]
+        if G is None:
+            G = np.zeros((nd, self.density_len), dtype=self.dtype)
+        if not isinstance(G, np.ndarray) or G.shape != (nd, self.density_len) or G.dtype != self.dtype or not G.flags.c_contiguous:
+            raise SctlAmdError("density gradients must be a contiguous %s array of shape (%d, %d)" % (self.dtype, nd, self.density_len))
+        p = lambda a: None if a.size == 0 else a.ctypes.data_as(C.c_void_p)
+        _check(lib().sctl_amd_near_apply_transpose_densities_host(self._h, nd, p(W), p(G)), "near_apply_transpose_densities_host")
+        return G
+
+    def apply_transpose_densities_device(self, W, G, stream=None):
+        """The same on torch CUDA tensors of shapes (nd, potential_len) and (nd, density_len), enqueued on `stream` (default: torch's
+        current stream); every row of G is accumulated into."""
+        import torch
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if W.dim() != 2 or G.dim() != 2 or G.shape[0] != W.shape[0] or W.shape[1] != self.potential_len or G.shape[1] != self.density_len:
+            raise SctlAmdError("weights and density gradients must have shapes (nd, %d) and (nd, %d)" % (self.potential_len, self.density_len))
+        if W.dtype != tdt or G.dtype != tdt:
+            raise SctlAmdError("weights and density gradients must be %s tensors" % tdt)
+        nd = W.shape[0]
+        with torch.cuda.device(W.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_near_apply_transpose_densities_device(self._h, nd, _t_ptr(W, tdt, nd * self.potential_len, "W"),
+                                                                        _t_ptr(G, tdt, nd * self.density_len, "G"), C.c_void_p(st.cuda_stream)),
+                   "near_apply_transpose_densities_device")
+        return G
 
     def close(self):
         if getattr(self, "_h", None):

@@ -29,7 +29,13 @@ potential is DirectOp.eval_potential (ComputePotential: far field, weights, targ
 backward DirectOp.eval_potential_transpose.  Both differentiate the densities only.
 
     u = sctl_amd.autograd.near_apply(near_op, f)                                     # torch CUDA tensor f of near_op.density_len values
-    u = sctl_amd.autograd.potential(direct_op, f_far, f_near)                        # torch CPU tensors"""
+    u = sctl_amd.autograd.potential(direct_op, f_far, f_near)                        # torch CPU tensors
+
+near_apply_densities and potential_densities are the same for several densities in one pass: NearOp.apply_densities_device with backward
+NearOp.apply_transpose_densities_device, DirectOp.eval_potential_densities with backward DirectOp.eval_potential_transpose_densities.
+
+    U = sctl_amd.autograd.near_apply_densities(near_op, F)                           # torch CUDA tensor F of shape (nd, near_op.density_len)
+    U = sctl_amd.autograd.potential_densities(direct_op, F_far, F_near)              # torch CPU tensors of shapes (nd, ...)"""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -196,3 +202,49 @@ def potential(op, f_far, f_near, digits=-1):
         if t.is_cuda:
             raise api.SctlAmdError("potential takes host tensors: %s is a CUDA tensor" % what)
     return _Potential.apply(op, f_far, f_near, digits)
+
+
+class _NearApplyDensities(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, op, F):
+        fn_ctx.op = op
+        return op.apply_densities_device(F.detach().contiguous(), torch.zeros((F.shape[0], op.potential_len), dtype=F.dtype, device=F.device))
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_U):
+        op = fn_ctx.op
+        return None, op.apply_transpose_densities_device(grad_U.contiguous(), torch.zeros((grad_U.shape[0], op.density_len), dtype=grad_U.dtype, device=grad_U.device))
+
+
+def near_apply_densities(op, F):
+    """NearOp.apply_densities_device from zero on a torch CUDA tensor of shape (nd, density_len) (a fresh result of shape (nd, potential_len)) that
+    autograd can differentiate with respect to the densities F: the backward is NearOp.apply_transpose_densities_device on the forward's stream,
+    and is once-differentiable."""
+    if F.dim() != 2 or F.shape[1] != op.density_len:
+        raise api.SctlAmdError("densities must have shape (nd, %d)" % op.density_len)
+    return _NearApplyDensities.apply(op, F)
+
+
+class _PotentialDensities(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, op, F_far, F_near, digits):
+        fn_ctx.op, fn_ctx.digits = op, digits
+        U = op.eval_potential_densities(F_far.detach().contiguous().numpy(), F_near.detach().contiguous().numpy(), digits=digits)
+        return torch.from_numpy(U)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_U):
+        G_far, G_near = fn_ctx.op.eval_potential_transpose_densities(grad_U.contiguous().numpy(), digits=fn_ctx.digits)
+        need = fn_ctx.needs_input_grad
+        return None, torch.from_numpy(G_far) if need[1] else None, torch.from_numpy(G_near) if need[2] else None, None
+
+
+def potential_densities(op, F_far, F_near, digits=-1):
+    """DirectOp.eval_potential_densities on torch HOST tensors of shapes (nd, Ns*SrcDim) and (nd, near density length) that autograd can
+    differentiate with respect to both: the backward is DirectOp.eval_potential_transpose_densities at the same digits."""
+    for what, t in (("F_far", F_far), ("F_near", F_near)):
+        if t.is_cuda:
+            raise api.SctlAmdError("potential_densities takes host tensors: %s is a CUDA tensor" % what)
+    return _PotentialDensities.apply(op, F_far, F_near, digits)

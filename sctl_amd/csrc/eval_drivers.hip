@@ -598,11 +598,12 @@ void normal_dot(int real, const void* v, const void* nrm, void* u, int64_t nt, i
     return 0;
   });
 }
-void normal_expand(int real, const void* w, const void* nrm, void* wf, int64_t nt, int k1r, hipStream_t st) {
+void normal_expand(int real, const void* w, const void* nrm, void* wf, int64_t nt, int k1r, int nd, hipStream_t st) {
   const unsigned nb = (unsigned)((nt * k1r * 3 + kBlock - 1) / kBlock);
   with_real(real, [&](auto zero) {
     using R = decltype(zero);
-    hipLaunchKernelGGL((normal_expand_kernel<R>), dim3(nb), dim3(kBlock), 0, st, (const R*)w, (const R*)nrm, (R*)wf, nt, k1r);
+    for (int m = 0; m < nd; m++)
+      hipLaunchKernelGGL((normal_expand_kernel<R>), dim3(nb), dim3(kBlock), 0, st, (const R*)w + (int64_t)m * nt * k1r, (const R*)nrm, (R*)wf + (int64_t)m * nt * k1r * 3, nt, k1r);
     return 0;
   });
 }

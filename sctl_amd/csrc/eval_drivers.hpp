@@ -108,7 +108,7 @@ void matrix_batch_launch(const KernelEntry& k, int real, const MatTile* tiles, i
 // ---- the operator handle's small pre/post kernels, one launch per density row (rows `stride` reals apart); the caller asks hipGetLastError ----
 void scale_density(int real, void* f, const void* w, int64_t Ns, int k0, int nd, hipStream_t st);                     // f[m][s][:] *= w[s]
 void normal_dot(int real, const void* v, const void* nrm, void* u, int64_t nt, int k1r, int nd, hipStream_t st);     // u[m][t][k] = sum_l v[m][t][k*3+l] nrm[t][l]
-void normal_expand(int real, const void* w, const void* nrm, void* wf, int64_t nt, int k1r, hipStream_t st);         // its adjoint, one row
+void normal_expand(int real, const void* w, const void* nrm, void* wf, int64_t nt, int k1r, int nd, hipStream_t st); // its adjoint: wf[m][t][k*3+l] = w[m][t][k] nrm[t][l]
 
 }  // namespace sctl_amd
 #pragma GCC visibility pop

@@ -345,6 +345,170 @@ __global__ void __launch_bounds__(kNearBlock) near_gemv_t_kernel(const NearWorkT
   }
 }
 
+// ---- several weight vectors through the transposed application (sctl_amd_near_apply_transpose_densities_*): G[m][f_off + s] += sum_t K[k_off +
+// s * trg_dof + t] * Wn[m][u_off + t], every operator entry read ONCE for the M vectors ----------------------------------------------------------
+// The gathered weights are INTERLEAVED: Wn[(near entry * k1 + k) * wn_stride + m], wn_stride = the widest form the handle has used.  One scattered
+// store of the gather and one weight load of a lane then cover the M values of an entry, which lie in one cache line.
+
+// near_gather_kernel for M rows: a target's displacement, count and scatter indices are read once.  Rows nact .. M-1 of a partly filled pass are
+// not read; their slots are written as zero.
+template <class R, int M>
+__global__ void __launch_bounds__(256) near_gather_multi_kernel(int64_t ntrg, int k1, int nact, const int64_t* __restrict__ scatter, const int64_t* __restrict__ trg_cnt,
+                                                                const int64_t* __restrict__ trg_dsp, const R* __restrict__ W, int64_t w_stride, R* __restrict__ Wn,
+                                                                int wn_stride) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ntrg * k1) return;
+  const int64_t i = idx / k1;
+  const int k = (int)(idx - i * k1);
+  const int64_t p0 = trg_dsp[i], p1 = p0 + trg_cnt[i];
+  if (p1 == p0) return;
+  R w[M];
+#pragma unroll
+  for (int m = 0; m < M; m++) w[m] = (m < nact) ? W[(int64_t)m * w_stride + idx] : R(0);
+  for (int64_t p = p0; p < p1; p++) {
+    R* dst = Wn + (scatter[p] * k1 + k) * wn_stride;
+#pragma unroll
+    for (int m = 0; m < M; m++) dst[m] = w[m];
+  }
+}
+
+// near_t_batch for M vectors: the same rows, columns, loads and order of additions in a lane; acc[ru * M + m] is the partial sum of row ru and vector m.
+// The sums then go through the SAME tree as near_t_batch's butterflies (offsets W/2 .. 1, own + partner at every level), but a level hands half of the
+// live sums to the partner and keeps the other half: S - 1 exchanges for S = (8 / NC) * M sums over the first log2(S) levels instead of S per level.
+// On return the lane l of a row group (l = lane & (W - 1)) holds in acc[0 .. n) the finished sums number first .. first + n - 1:
+//   W >= S : n = 1, first = l / (W / S), the same bits in all W / S lanes of that run;       W < S : n = S / W, first = l * n.
+template <class R, int NC, int M>
+__device__ __forceinline__ void near_t_batch_m(const R* __restrict__ Kb, const R* __restrict__ We, int ws, int ld, int rb, int r1, int c0, int c1, int lw, int lane,
+                                               R (&acc)[(8 / NC) * M]) {
+  constexpr int NR = 8 / NC, S = NR * M;
+  const int W = 1 << lw, step = 64 >> lw, row0 = rb + (lane >> lw), l = lane & (W - 1);
+#pragma unroll
+  for (int i = 0; i < S; i++) acc[i] = 0;
+  const bool rows_full = rb + NR * step <= r1;
+  for (int cb = c0; cb < c1; cb += NC * W) {
+    R kv[8], wv[NC][M];
+    if (rows_full && cb + NC * W <= c1) {     // whole batch inside the block: no predicates
+#pragma unroll
+      for (int cu = 0; cu < NC; cu++)
+#pragma unroll
+        for (int m = 0; m < M; m++) wv[cu][m] = We[(int64_t)(cb + cu * W + l) * ws + m];
+#pragma unroll
+      for (int u = 0; u < 8; u++) kv[u] = __builtin_nontemporal_load(Kb + (int64_t)(row0 + (u / NC) * step) * ld + (cb + (u % NC) * W + l));
+      __asm__ volatile("" ::: "memory");     // (keeps the two paths' loads apart: none sinks below the join to serve both)
+    } else {
+#pragma unroll
+      for (int cu = 0; cu < NC; cu++) {
+        const int t = cb + cu * W + l;
+#pragma unroll
+        for (int m = 0; m < M; m++) wv[cu][m] = (t < c1) ? We[(int64_t)t * ws + m] : R(0);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int r = row0 + (u / NC) * step, t = cb + (u % NC) * W + l;
+        kv[u] = (r < r1 && t < c1) ? __builtin_nontemporal_load(Kb + (int64_t)r * ld + t) : R(0);
+      }
+      __asm__ volatile("" ::: "memory");
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u++)
+#pragma unroll
+      for (int m = 0; m < M; m++) acc[(u / NC) * M + m] += kv[u] * wv[u % NC][m];
+  }
+  int o = W >> 1;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {               // level j: offset W >> (j + 1), S >> (j + 1) sums stay
+    const int h = S >> (j + 1);
+    if (o > 0) {                              // (wave-uniform)
+      if (h >= 1) {
+        const bool up = (lane & o) != 0;
+#pragma unroll
+        for (int i = 0; i < (h >= 1 ? h : 1); i++) {
+          const R keep = up ? acc[i + h] : acc[i], send = up ? acc[i] : acc[i + h];
+          acc[i] = keep + __shfl_xor(send, o);
+        }
+      } else {
+        acc[0] += __shfl_xor(acc[0], o);
+      }
+      o >>= 1;
+    }
+  }
+}
+
+// which finished sums of near_t_batch_m this lane owns, and whether it is the one lane that stores them
+template <int S>
+__device__ __forceinline__ void near_t_owned(int lw, int lane, int& first, int& n, bool& writer) {
+  constexpr int LS = S == 1 ? 0 : S == 2 ? 1 : S == 4 ? 2 : S == 8 ? 3 : S == 16 ? 4 : S == 32 ? 5 : 6;
+  static_assert((1 << LS) == S, "S is a power of two up to 64");
+  const int l = lane & ((1 << lw) - 1);
+  if (lw >= LS) { n = 1; first = l >> (lw - LS); writer = (l & ((1 << (lw - LS)) - 1)) == 0; }
+  else { n = S >> lw; first = l << (LS - lw); writer = true; }
+}
+
+// one wave, all rows of an item; the owner lane of a sum adds it to its entry of G
+template <class R, int NC, int M>
+__device__ __forceinline__ void near_t_item_m(const NearWorkT& w, const R* __restrict__ K, const R* __restrict__ Wn, int ws, R* __restrict__ G, int64_t g_stride, int nact,
+                                              int lane) {
+  constexpr int NR = 8 / NC, S = NR * M;
+  const int step = 64 >> w.lw;
+  int first, n;
+  bool writer;
+  near_t_owned<S>(w.lw, lane, first, n, writer);
+  for (int rb = w.r0; rb < w.r1; rb += NR * step) {
+    R acc[S];
+    near_t_batch_m<R, NC, M>(K + w.k_off, Wn + w.u_off * ws, ws, w.trg_dof, rb, w.r1, 0, w.trg_dof, w.lw, lane, acc);
+    const int row0 = rb + (lane >> w.lw);
+#pragma unroll
+    for (int i = 0; i < S; i++) {
+      const int id = first + i, m = id % M, r = row0 + (id / M) * step;
+      if (i < n && writer && m < nact && r < w.r1) G[(int64_t)m * g_stride + w.f_off + r] += acc[i];
+    }
+  }
+}
+
+// near_gemv_t_kernel for M weight vectors per pass: its work list, lane mapping, loads and trees.  A split item leaves (8 / NC) * M sums per wave in LDS.
+template <class R, int M>
+__global__ void __launch_bounds__(kNearBlock) __attribute__((amdgpu_waves_per_eu(2, 8)))
+near_gemm_t_kernel(const NearWorkT* __restrict__ split_work, int64_t n_split, const NearWorkT* __restrict__ wave_work, int64_t n_wave, const R* __restrict__ K,
+                   const R* __restrict__ Wn, int ws, int nact, R* __restrict__ G, int64_t g_stride) {
+  __shared__ R part[kRowGroups][8 * M];
+  const int lane = threadIdx.x & (kCols - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kCols));
+  for (int64_t wi = blockIdx.x; wi < n_split; wi += gridDim.x) {
+    const NearWorkT w = split_work[wi];
+    const int per = ((w.trg_dof + kCols - 1) / kCols + kRowGroups - 1) / kRowGroups * kCols;   // columns per wave
+    const int c0 = wave * per < w.trg_dof ? wave * per : w.trg_dof, c1 = c0 + per < w.trg_dof ? c0 + per : w.trg_dof;
+    const R* We = Wn + w.u_off * ws;
+    int S;                    // sums of this item: rows in flight x M, sum number = row * M + m
+    if (w.nc == 8) {
+      R a[M];
+      near_t_batch_m<R, 8, M>(K + w.k_off, We, ws, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, a);
+      S = M;
+      if ((lane & (64 / M - 1)) == 0) part[wave][lane / (64 / M)] = a[0];
+    } else if (w.nc == 4) {   // two rows, four chunks each
+      R a[2 * M];
+      near_t_batch_m<R, 4, M>(K + w.k_off, We, ws, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, a);
+      S = 2 * M;
+      if ((lane & (32 / M - 1)) == 0) part[wave][lane / (32 / M)] = a[0];
+    } else {
+      R a[8 * M];
+      near_t_batch_m<R, 1, M>(K + w.k_off, We, ws, w.trg_dof, w.r0, w.r1, c0, c1, 6, lane, a);
+      S = 8 * M;
+      if ((lane & (8 / M - 1)) == 0) part[wave][lane / (8 / M)] = a[0];
+    }
+    __syncthreads();
+    const int id = (int)threadIdx.x, m = id % M, r = w.r0 + id / M;
+    if (id < S && m < nact && r < w.r1)
+      G[(int64_t)m * g_stride + w.f_off + r] += (part[0][id] + part[1][id]) + (part[2][id] + part[3][id]);
+    __syncthreads();
+  }
+  for (int64_t wi = (int64_t)blockIdx.x * kRowGroups + wave; wi < n_wave; wi += (int64_t)gridDim.x * kRowGroups) {
+    const NearWorkT w = wave_work[wi];
+    if (w.nc == 1) near_t_item_m<R, 1, M>(w, K, Wn, ws, G, g_stride, nact, lane);
+    else if (w.nc == 2) near_t_item_m<R, 2, M>(w, K, Wn, ws, G, g_stride, nact, lane);
+    else if (w.nc == 4) near_t_item_m<R, 4, M>(w, K, Wn, ws, G, g_stride, nact, lane);
+    else near_t_item_m<R, 8, M>(w, K, Wn, ws, G, g_stride, nact, lane);
+  }
+}
+
 struct DevMem {
   void* p = nullptr;
   ~DevMem() { if (p) (void)hipFree(p); }
@@ -387,6 +551,9 @@ struct sctl_amd_near {
   DevMem work_t, Wn;            // work_t: the split items, then the wave items; Wn: W in near-list order, [n_near * k1]
   int64_t n_split = 0, n_wave_t = 0;
   bool t_ready = false;
+  // several weight vectors: allocated on first use
+  DevMem Wn_m;                  // [n_near * k1][mt_cap] (interleaved), mt_cap = the widest pass used so far; zero-filled when grown
+  int mt_cap = 0;
   hipStream_t st = nullptr;
   ~sctl_amd_near() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -540,9 +707,66 @@ int apply_transpose_on_stream(sctl_amd_near* h, const R* W, R* G, hipStream_t st
   return SCTL_AMD_OK;
 }
 
+// The transposed pass for `left` weight vectors still to do: near_pass_width's rule over the shipped forms, which are 2 and 4 in fp64 and 2 in fp32.
+// Measured on the 2.8 GB operator: the fp32 form of 4 took 1.28 x the time of four single calls and is not built; a form of 8 does not
+// fit 256 vector registers without scratch in either precision.
+template <class R> constexpr int near_t_widest() { return sizeof(R) == 8 ? 4 : 2; }
+template <class R> inline int near_t_pass_width(int left) { return left <= 2 ? 2 : near_t_widest<R>(); }
+
+template <class R, int M>
+int near_t_pass(sctl_amd_near* h, int nact, const R* W, R* G, hipStream_t st) {
+  const int64_t n = h->ntrg * h->k1;
+  hipLaunchKernelGGL((near_gather_multi_kernel<R, M>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->ntrg, h->k1, nact, (const int64_t*)h->scatter.p,
+                     (const int64_t*)h->trg_cnt.p, (const int64_t*)h->trg_dsp.p, W, n, (R*)h->Wn_m.p, h->mt_cap);
+  NEAR_TRY(hipGetLastError());
+  const int64_t resident = (int64_t)h->cus * 8;
+  const int64_t groups = h->n_split + (h->n_wave_t + kRowGroups - 1) / kRowGroups;
+  const unsigned grid = (unsigned)(groups < resident * 4 ? groups : resident * 4);
+  const NearWorkT* wl = (const NearWorkT*)h->work_t.p;
+  hipLaunchKernelGGL((near_gemm_t_kernel<R, M>), dim3(grid), dim3(kNearBlock), 0, st, wl, h->n_split, wl + h->n_split, h->n_wave_t, (const R*)h->K.p,
+                     (const R*)h->Wn_m.p, h->mt_cap, nact, G, h->f_len);
+  NEAR_TRY(hipGetLastError());
+  return SCTL_AMD_OK;
+}
+
+// nd >= 2 weight vectors, row-major: passes of the widest form, the last pass on the narrowest form that takes what is left; a single vector left over
+// goes through the single-vector kernels.
+template <class R>
+int apply_transpose_densities_on_stream(sctl_amd_near* h, int nd, const R* W, R* G, hipStream_t st) {
+  (void)hipGetLastError();
+  if (h->n_split + h->n_wave_t == 0) return SCTL_AMD_OK;
+  const int widest = near_t_pass_width<R>(nd);
+  if (widest > h->mt_cap) {   // interleaved with the stride of the widest pass: an entry that the gather never writes (near_scatter_index no permutation) stays zero
+    const size_t bytes = (size_t)widest * h->n_near * h->k1 * sizeof(R);
+    h->mt_cap = 0;
+    NEAR_TRY(h->Wn_m.realloc(bytes));
+    NEAR_TRY(hipMemsetAsync(h->Wn_m.p, 0, bytes, st));
+    h->mt_cap = widest;
+  }
+  const int64_t u_len = h->ntrg * h->k1;
+  for (int m0 = 0; m0 < nd;) {
+    const int left = nd - m0;
+    const R* Wp = W + (int64_t)m0 * u_len;
+    R* Gp = G + (int64_t)m0 * h->f_len;
+    if (left == 1) return apply_transpose_on_stream<R>(h, Wp, Gp, st);
+    const int M = near_t_pass_width<R>(left), nact = left < M ? left : M;
+    const int rc = (M == 2) ? near_t_pass<R, 2>(h, nact, Wp, Gp, st) : near_t_pass<R, near_t_widest<R>()>(h, nact, Wp, Gp, st);
+    if (rc) return rc;
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+
 int check_apply_transpose(const sctl_amd_near* h, const void* W, const void* G) {
   if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
   if ((h->ntrg > 0 && !W) || (h->f_len > 0 && !G)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or density-gradient array");
+  return SCTL_AMD_OK;
+}
+
+int check_apply_transpose_densities(const sctl_amd_near* h, int nd, const void* W, const void* G) {
+  if (!h) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null near-field handle");
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of weight vectors");
+  if (nd > 0 && ((h->ntrg > 0 && !W) || (h->f_len > 0 && !G))) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or density-gradient array");
   return SCTL_AMD_OK;
 }
 
@@ -743,6 +967,56 @@ int sctl_amd_near_apply_transpose_host(sctl_amd_near* h, const void* W, void* G)
       add_into(h->real, (char*)G + (size_t)f_off * rs, sf + (size_t)f_off * rs, sd);
     }
     f_off += sd;
+  }
+  return SCTL_AMD_OK;
+}
+
+// nd == 1 goes through the single-vector entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+int sctl_amd_near_apply_transpose_densities_device(sctl_amd_near* h, int nd, const void* W, void* G, void* stream) {
+  const int rc0 = check_apply_transpose_densities(h, nd, W, G);
+  if (rc0 || nd == 0) return rc0;
+  if (nd == 1) return sctl_amd_near_apply_transpose_device(h, W, G, stream);
+  if (h->k_len == 0 || h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  const int rc = prepare_transpose(h, (hipStream_t)stream);
+  if (rc) return rc;
+  return with_real(h->real, [&](auto zero) { using R = decltype(zero); return apply_transpose_densities_on_stream<R>(h, nd, (const R*)W, (R*)G, (hipStream_t)stream); });
+}
+
+int sctl_amd_near_apply_transpose_densities_host(sctl_amd_near* h, int nd, const void* W, void* G) {
+  const int rc0 = check_apply_transpose_densities(h, nd, W, G);
+  if (rc0 || nd == 0) return rc0;
+  if (nd == 1) return sctl_amd_near_apply_transpose_host(h, W, G);
+  if (h->k_len == 0 || h->n_near == 0 || h->ntrg == 0) return SCTL_AMD_OK;
+  const size_t rs = real_size(h->real);
+  const size_t bf = (size_t)nd * h->f_len * rs, bu = (size_t)nd * h->ntrg * h->k1 * rs;
+  DeviceScope dev_scope(h->device);
+  NEAR_TRY(dev_scope.err);
+  if (nd > h->nd_cap) {   // the staging and the device arrays of the forward several-densities host entry, roles swapped
+    h->nd_cap = 0;
+    NEAR_TRY(h->F_m.realloc(bf));
+    NEAR_TRY(h->U_m.realloc(bu));
+    NEAR_TRY(h->stage_m.realloc(bf + bu + 512));
+    h->nd_cap = nd;
+  }
+  char* sf = (char*)h->stage_m.p;
+  char* su = sf + ((bf + 255) & ~(size_t)255);
+  std::memcpy(su, W, bu);
+  NEAR_TRY(hipMemcpyAsync(h->U_m.p, su, bu, hipMemcpyHostToDevice, h->st));
+  NEAR_TRY(hipMemsetAsync(h->F_m.p, 0, bf, h->st));
+  const int rc = sctl_amd_near_apply_transpose_densities_device(h, nd, h->U_m.p, h->F_m.p, h->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  NEAR_TRY(hipMemcpyAsync(sf, h->F_m.p, bf, hipMemcpyDeviceToHost, h->st));
+  NEAR_TRY(hipStreamSynchronize(h->st));
+  // every row: G += N^T W over the entries some block owns; the others keep their bits
+  for (int m = 0; m < nd; m++) {
+    int64_t f_off = (int64_t)m * h->f_len;
+    for (int64_t e = 0; e < h->nelem; e++) {
+      const int64_t sd = h->e_nds[(size_t)e] * h->k0;
+      if (h->e_kcnt[(size_t)e] != 0 && h->e_near[(size_t)e] > 0) add_into(h->real, (char*)G + (size_t)f_off * rs, sf + (size_t)f_off * rs, sd);
+      f_off += sd;
+    }
   }
   return SCTL_AMD_OK;
 }

@@ -482,26 +482,32 @@ int sctl_amd_op_eval_dist(sctl_amd_op* op, sctl_amd_comm* comm, int64_t Ns_local
   const int arg_rc = comm_agree(comm, check_op_eval(op, v_src_local, nullptr, v_trg, ctx, ctx_bytes, comm, Ns_local), "sctl_amd_op_eval_dist");
   return arg_rc ? arg_rc : op_eval_body(op, 1, v_src_local, nullptr, v_trg, accumulate, digits, ctx, comm, Ns_local);
 }
-// The adjoint of op_eval_impl for one weight vector: g_far = D_w A^T C_n^T w and, with_near, g_near = N^T w.  Every device works on its
-// target slab; the partial results wait in the devices' staging buffers and are added on the host in device order.
-static int op_eval_transpose_impl(sctl_amd_op* op, const void* w_trg, void* g_far, void* g_near, bool with_near, int accumulate, int digits, const void* ctx,
-                                  int ctx_bytes) {
+// The adjoint of op_eval_body for nd >= 1 weight vectors, row-major: g_far[m] = D_w A^T C_n^T w[m] and, with_near, g_near[m] = N^T w[m].  Every device
+// works on its target slab of every row; the partial results wait in the devices' staging buffers and are added on the host in device order, row by row.
+// One row takes the single transposed driver and near apply, several take the several-vectors forms: that keeps nd == 1 bit-identical to what it was.
+static int op_eval_transpose_impl(sctl_amd_op* op, int nd, const void* w_trg, void* g_far, void* g_near, bool with_near, int accumulate, int digits,
+                                  const void* ctx, int ctx_bytes) {
   if (!op) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of weight vectors");
   const KernelEntry& k = *op->k;
   int rc0 = with_near ? check_near_attached(op) : SCTL_AMD_OK;
   if (rc0 == SCTL_AMD_OK) rc0 = check_ctx(k, ctx, ctx_bytes);
   if (rc0) return rc0;
-  if ((op->Nt > 0 && !w_trg) || (op->Ns > 0 && !g_far) || (with_near && op->near_f_len > 0 && !g_near))
+  if (nd > 0 && ((op->Nt > 0 && !w_trg) || (op->Ns > 0 && !g_far) || (with_near && op->near_f_len > 0 && !g_near)))
     return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null weight or density-gradient array");
   if (!has_transpose(k)) return no_transpose(k);
+  if (nd == 0) return SCTL_AMD_OK;
   const size_t rs = real_size(op->real);
   const int64_t Ns = op->Ns;
   const int k1w = op->have_trg_normals ? k.k1 / 3 : k.k1;   // components of w per target
-  const size_t fbytes = (size_t)Ns * k.k0 * rs, nbytes = with_near ? (size_t)op->near_f_len * rs : 0, wrow = (size_t)k1w * rs;
-  std::vector<char> sorted;   // w in the operator's own (Morton) target order
+  const size_t frow = (size_t)Ns * k.k0 * rs, nrow = with_near ? (size_t)op->near_f_len * rs : 0, wrow = (size_t)k1w * rs;
+  const size_t fbytes = (size_t)nd * frow, nbytes = (size_t)nd * nrow;
+  std::vector<char> sorted;   // every row of w in the operator's own (Morton) target order
   if (!op->perm.empty()) {
-    sorted.resize((size_t)op->Nt * wrow);
-    for (int64_t i = 0; i < op->Nt; i++) std::memcpy(&sorted[(size_t)i * wrow], (const char*)w_trg + (size_t)op->perm[(size_t)i] * wrow, wrow);
+    sorted.resize((size_t)nd * op->Nt * wrow);
+    for (int m = 0; m < nd; m++)
+      for (int64_t i = 0; i < op->Nt; i++)
+        std::memcpy(&sorted[((size_t)m * op->Nt + (size_t)i) * wrow], (const char*)w_trg + ((size_t)m * op->Nt + (size_t)op->perm[(size_t)i]) * wrow, wrow);
   }
   const char* wsrc = sorted.empty() ? (const char*)w_trg : sorted.data();
   std::vector<const char*> part_far(op->devs.size(), nullptr), part_near(op->devs.size(), nullptr);
@@ -509,31 +515,39 @@ static int op_eval_transpose_impl(sctl_amd_op* op, const void* w_trg, void* g_fa
     const int64_t nt = d.t1 - d.t0;
     if (nt == 0) return SCTL_AMD_OK;
     const size_t g = (size_t)(&d - op->devs.data());
-    const size_t wbytes = (size_t)nt * wrow;
+    const size_t wslab = (size_t)nt * wrow, wbytes = (size_t)nd * wslab;
     DeviceScope dev_scope(d.device);
     HIP_TRY(dev_scope.err);
     HIP_TRY(grow(&d.f, &d.cap_f, fbytes));
-    HIP_TRY(grow(&d.v, &d.cap_v, (size_t)nt * k.k1 * rs));
+    HIP_TRY(grow(&d.v, &d.cap_v, (size_t)nd * nt * k.k1 * rs));
     if (op->have_trg_normals) HIP_TRY(grow(&d.u, &d.cap_u, wbytes));
     HIP_TRY(d.stage.reserve(pad256(wbytes) + pad256(fbytes) + pad256(nbytes)));
-    void* w_dev = op->have_trg_normals ? d.u : d.v;   // the slab of w as the caller gave it: what the near field takes
-    HIP_TRY(upload(w_dev, wsrc + (size_t)d.t0 * wrow, wbytes, d.stage, d.st));
-    if (op->have_trg_normals) {   // w_full[t][k*3+l] = w[t][k] n_trg[t][l]: the adjoint of the contraction with the target normal
-      normal_expand(op->real, d.u, d.nt, d.v, nt, k1w, d.st);
+    void* w_dev = op->have_trg_normals ? d.u : d.v;   // the slab of every row of w as the caller gave it: what the near field takes
+    {   // this slab of every row, rows back to back, down once
+      char* q = d.stage.take(wbytes);
+      for (int m = 0; m < nd; m++) std::memcpy(q + (size_t)m * wslab, wsrc + ((size_t)m * op->Nt + (size_t)d.t0) * wrow, wslab);
+      HIP_TRY(hipMemcpyAsync(w_dev, q, wbytes, hipMemcpyHostToDevice, d.st));
+    }
+    if (op->have_trg_normals) {   // w_full[m][t][k*3+l] = w[m][t][k] n_trg[t][l]: the adjoint of the contraction with the target normal
+      normal_expand(op->real, d.u, d.nt, d.v, nt, k1w, nd, d.st);
       HIP_TRY(hipGetLastError());
     }
     if (fbytes) HIP_TRY(hipMemsetAsync(d.f, 0, fbytes, d.st));
     int rc = SCTL_AMD_OK;
-    if (Ns > 0) rc = eval_transpose_device(k, op->real, nt, Ns, d.xt, d.xs, d.xn, d.v, d.f, digits, ctx, d.st);
+    if (Ns == 0) {}
+    else if (nd == 1) rc = eval_transpose_device(k, op->real, nt, Ns, d.xt, d.xs, d.xn, d.v, d.f, digits, ctx, d.st);
+    else rc = eval_transpose_densities_device(k, op->real, nd, nt, Ns, d.xt, d.xs, d.xn, d.v, d.f, digits, ctx, d.st);
     if (rc) return rc;
     if (op->have_weights && Ns > 0) {   // the adjoint of density x quadrature weights is the same scaling
-      scale_density(op->real, d.f, d.w, Ns, k.k0, 1, d.st);
+      scale_density(op->real, d.f, d.w, Ns, k.k0, nd, d.st);
       HIP_TRY(hipGetLastError());
     }
     const bool near_here = nbytes && op->near[g];
     if (near_here) {
+      HIP_TRY(grow(&op->near_f[g], &op->near_f_cap[g], nbytes));   // (one row fits what sctl_amd_op_set_near allocated)
       HIP_TRY(hipMemsetAsync(op->near_f[g], 0, nbytes, d.st));
-      rc = sctl_amd_near_apply_transpose_device(op->near[g], w_dev, op->near_f[g], d.st);
+      rc = nd == 1 ? sctl_amd_near_apply_transpose_device(op->near[g], w_dev, op->near_f[g], d.st)
+                   : sctl_amd_near_apply_transpose_densities_device(op->near[g], nd, w_dev, op->near_f[g], d.st);
       if (rc) return rc;
     }
     char* out_f = d.stage.take(fbytes);
@@ -546,7 +560,7 @@ static int op_eval_transpose_impl(sctl_amd_op* op, const void* w_trg, void* g_fa
     return SCTL_AMD_OK;
   });
   if (rc_all) return rc_all;
-  auto combine = [&](void* out, const std::vector<const char*>& parts, size_t bytes) {   // device order: a fixed order
+  auto combine = [&](void* out, const std::vector<const char*>& parts, size_t bytes) {   // device order: a fixed order (the rows lie back to back)
     if (!bytes) return;
     if (!accumulate) std::memset(out, 0, bytes);
     for (const char* p : parts)
@@ -558,12 +572,23 @@ static int op_eval_transpose_impl(sctl_amd_op* op, const void* w_trg, void* g_fa
 }
 
 int sctl_amd_op_eval_transpose(sctl_amd_op* op, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx, int ctx_bytes) {
-  return op_eval_transpose_impl(op, w_trg, g_src, nullptr, false, accumulate, digits, ctx, ctx_bytes);
+  return op_eval_transpose_impl(op, 1, w_trg, g_src, nullptr, false, accumulate, digits, ctx, ctx_bytes);
 }
 
 int sctl_amd_op_eval_potential_transpose(sctl_amd_op* op, const void* w_trg, void* g_src_far, void* g_near, int accumulate, int digits, const void* ctx,
                                          int ctx_bytes) {
-  return op_eval_transpose_impl(op, w_trg, g_src_far, g_near, true, accumulate, digits, ctx, ctx_bytes);
+  return op_eval_transpose_impl(op, 1, w_trg, g_src_far, g_near, true, accumulate, digits, ctx, ctx_bytes);
+}
+
+// nd rows in one pass; nd == 1 is the single entry (op_eval_transpose_impl takes the single drivers for it), nd == 0 a no-op after the argument checks.
+int sctl_amd_op_eval_transpose_densities(sctl_amd_op* op, int nd, const void* w_trg, void* g_src, int accumulate, int digits, const void* ctx,
+                                         int ctx_bytes) {
+  return op_eval_transpose_impl(op, nd, w_trg, g_src, nullptr, false, accumulate, digits, ctx, ctx_bytes);
+}
+
+int sctl_amd_op_eval_potential_transpose_densities(sctl_amd_op* op, int nd, const void* w_trg, void* g_src_far, void* g_near, int accumulate, int digits,
+                                                   const void* ctx, int ctx_bytes) {
+  return op_eval_transpose_impl(op, nd, w_trg, g_src_far, g_near, true, accumulate, digits, ctx, ctx_bytes);
 }
 
 static void op_release_near(sctl_amd_op* op) {
