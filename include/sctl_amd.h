@@ -478,7 +478,7 @@ int sctl_amd_eval_lists_host(int kernel, int real, int64_t nlists, const int64_t
  * unknown bit, and evaluating a direction the plan was not made for, are SCTL_AMD_ERR_BAD_ARGUMENT; a kernel without a transposed form
  * (a plugin functor without pair_t) gets SCTL_AMD_ERR_UNKNOWN_KERNEL from a create that asks for TRANSPOSE.  The counters grow by the
  * plan's pairs.  _host reuses the handle's stream, staging and device buffers (w_trg has the size of v_trg, g_src that of v_src).
- * Not built: several densities, geometry gradients and several GPUs over lists. */
+ * Several weight vectors: sctl_amd_lists_eval_transpose_densities_* below.  Not built: geometry gradients and several GPUs over lists. */
 #define SCTL_AMD_LISTS_FORWARD 1
 #define SCTL_AMD_LISTS_TRANSPOSE 2
 int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
@@ -512,6 +512,31 @@ int sctl_amd_lists_eval_densities_host(sctl_amd_lists* plan, int nd, const void*
 int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
                                        const int64_t* src_off, const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src,
                                        const void* n_src, const void* v_src, void* v_trg, int digits, const void* ctx, int ctx_bytes, int device);
+
+/* Several weight vectors through the transposed sum over the lists of one plan: row-major w_trg[nd][Nt*TrgDim] and g_src[nd][Ns*SrcDim],
+ * every row ACCUMULATED into,
+ *     g_src[m][s*SrcDim + k0] += scale * sum_{l : s in source range l} sum_{t in target range l} sum_k1 U(x_t - x_s, n_s)[k0][k1] * w_trg[m][t*TrgDim + k1].
+ * The plan is the transposed plan of sctl_amd_lists_create_directions and does not depend on nd.  Checks, in order: a null handle; the
+ * context (SCTL_AMD_ERR_BAD_CONTEXT whatever nd is); nd < 0 (SCTL_AMD_ERR_BAD_ARGUMENT); a plan made without SCTL_AMD_LISTS_TRANSPOSE
+ * (SCTL_AMD_ERR_BAD_ARGUMENT, as sctl_amd_lists_eval_transpose_*).  nd == 0 does nothing and touches nothing, nd == 1 IS
+ * sctl_amd_lists_eval_transpose_* (same launch, same bits); a plan without transposed work items returns OK without a device and without
+ * reading the arrays.  A call is ONE launch per pass, all on the same stream: passes of the kernel's widest form (8, 4 or 2 weight
+ * vectors, per kernel and precision: DESIGN.md §4.15), then the narrowest form that holds the rest; a single row left over takes the
+ * single-vector transposed list kernel, and a plugin kernel with pair_t (no several-vectors form) runs its rows one at a time on the same
+ * stream.  Within a several-vectors pass a row's terms may be summed in another grouping than the single-vector kernel's (rel-L2 ~1e-16
+ * in fp64); there are no atomics and no workspace: results are bit-identical from run to run.  fp32 runs the exact vector-pipe pair.  The
+ * counters grow by nd x the plan's pairs.  _host: coordinates and normals are staged once, the nd weight rows go up in one transfer, the nd
+ * result rows come back in one; sources that ARE the targets (one array) keep one device copy; the handle's stream, staging and device
+ * buffers are reused and grown as needed. */
+int sctl_amd_lists_eval_transpose_densities_device(sctl_amd_lists* plan, int nd, const void* r_trg, const void* r_src, const void* n_src,
+                                                   const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream);
+int sctl_amd_lists_eval_transpose_densities_host(sctl_amd_lists* plan, int nd, const void* r_trg, const void* r_src, const void* n_src,
+                                                 const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes);
+/* One-shot form (plan TRANSPOSE, evaluate, release), HOST arrays; nd < 0 comes back before the plan is made. */
+int sctl_amd_eval_lists_transpose_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
+                                                 const int64_t* src_off, const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg,
+                                                 const void* r_src, const void* n_src, const void* w_trg, void* g_src, int digits, const void* ctx,
+                                                 int ctx_bytes, int device);
 
 /* ---- accounting (the reference's Profile::IncrementCounter(FLOP, Ns*Nt*FLOPS()), generic-kernel.txx:188) ---- */
 /* Process-wide counters, updated atomically by every eval / kernel_matrix call. */

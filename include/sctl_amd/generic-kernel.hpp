@@ -255,6 +255,34 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_lists_transpose_host");
   }
 
+  // EvalListsTranspose for several weight vectors in one launch per pass (sctl_amd_eval_lists_transpose_densities_host): row m of W (nd x Nt*TrgDim)
+  // is a vector of target weights, row m of G (nd x Ns*SrcDim) what EvalListsTranspose gives for it — A^T W for the block EvalListsDensities sent
+  // through A.  G follows EvalDensities' rule: the right size is accumulated into, any other is resized and zeroed.  nd == 1 is EvalListsTranspose's
+  // own path.
+  template <class Real, Integer digits = -1>
+  void EvalListsTransposeDensities(Matrix<Real>& G, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Matrix<Real>& W,
+                                   const Vector<Long>& trg_off, const Vector<Long>& trg_cnt, const Vector<Long>& src_off, const Vector<Long>& src_cnt) const {
+    static_assert(sizeof(Long) == sizeof(int64_t), "Long must be 64 bits wide");
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nl = trg_off.Dim(), nd = W.Dim(0);
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(W.Dim(1) == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(trg_cnt.Dim() == nl && src_off.Dim() == nl && src_cnt.Dim() == nl);
+    SCTL_AMD_ASSERT(nd <= 0x7fffffff);
+    if (G.Dim(0) != nd || G.Dim(1) != Ns * KDIM0) {
+      G.ReInit(nd, Ns * KDIM0);
+      G.SetZero();
+    }
+    if (!nl || !nd) return;
+    RequireSupported();
+    auto i64 = [](const Vector<Long>& v) { return reinterpret_cast<const int64_t*>(&v[0]); };
+    const int rc = sctl_amd_eval_lists_transpose_densities_host(DeviceKernelId(), RealTag<Real>::value, (int)nd, nl, i64(trg_off), i64(trg_cnt), i64(src_off),
+                                                                i64(src_cnt), Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, W.begin(),
+                                                                G.begin(), (int)digits, ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_lists_transpose_densities_host");
+  }
+
   // The gradients of L = <w_trg, A v_src> with respect to the geometry (sctl_amd_eval_grad_host; not in the reference): with d = x_t - x_s and
   // phi_ts = sum_k0 sum_k1 w_trg[t*TrgDim + k1] U(d, n_s)[k0][k1] v_src[s*SrcDim + k0],
   //   g_trg[t*DIM + j] += scale sum_s d phi_ts / d d_j,    g_src[s*DIM + j] -= scale sum_t d phi_ts / d d_j,    g_nrm[s*DIM + j] += scale sum_t d phi_ts / d n_j.

@@ -34,6 +34,7 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_transpose_device", "sctl_amd_eval_transpose_host", "sctl_amd_eval_transpose_plan",
            "sctl_amd_lists_create_directions", "sctl_amd_lists_eval_transpose_device", "sctl_amd_lists_eval_transpose_host", "sctl_amd_lists_transpose_info",
            "sctl_amd_eval_lists_transpose_host",
+           "sctl_amd_lists_eval_transpose_densities_device", "sctl_amd_lists_eval_transpose_densities_host", "sctl_amd_eval_lists_transpose_densities_host",
            "sctl_amd_eval_grad_device", "sctl_amd_eval_grad_host", "sctl_amd_eval_grad_plan",
            "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose",
            "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan",
@@ -142,6 +143,9 @@ def lib():
     L.sctl_amd_lists_eval_transpose_host.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci]
     L.sctl_amd_lists_transpose_info.argtypes = [vp, pi64, pi64, pi64]
     L.sctl_amd_eval_lists_transpose_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
+    L.sctl_amd_lists_eval_transpose_densities_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_lists_eval_transpose_densities_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, ci]
+    L.sctl_amd_eval_lists_transpose_densities_host.argtypes = [ci, ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_transpose_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_transpose_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -1123,6 +1127,45 @@ class ListsPlan:
                    "lists_eval_densities_device")
         return V_trg
 
+    def eval_transpose_densities_host(self, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1):
+        """eval_transpose_host() for nd weight vectors in one launch per pass (sctl_amd_lists_eval_transpose_densities_host): W_trg of shape
+        (nd, Nt*TrgDim), returns (nd, Ns*SrcDim); a G_src of that shape is accumulated into, otherwise a fresh zeroed result is returned."""
+        dt, i = self.dtype, self.info
+        W_trg = np.asarray(W_trg)
+        if W_trg.ndim != 2 or W_trg.shape[1] != self.Nt * i["k1"]:
+            raise SctlAmdError("weights must have shape (nd, %d)" % (self.Nt * i["k1"]))
+        nd = W_trg.shape[0]
+        if G_src is None or G_src.shape != (nd, self.Ns * i["k0"]):
+            G_src = np.zeros((nd, self.Ns * i["k0"]), dtype=dt)
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        _check(lib().sctl_amd_lists_eval_transpose_densities_host(self._h, nd, _np_ptr(r_trg, dt, self.Nt * 3, "r_trg"), _np_ptr(r_src, dt, self.Ns * 3, "r_src"),
+                                                                  _np_ptr(n_src, dt, self.Ns * i["nd"], "n_src"),
+                                                                  _np_ptr(W_trg, dt, nd * self.Nt * i["k1"], "W_trg"),
+                                                                  _np_ptr(G_src, dt, nd * self.Ns * i["k0"], "G_src"), digits, cp, cb),
+               "lists_eval_transpose_densities_host")
+        return G_src
+
+    def eval_transpose_densities_device(self, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1, stream=None):
+        """The same on torch CUDA tensors on the plan's device (sctl_amd_lists_eval_transpose_densities_device), enqueued on `stream` (default:
+        torch's current stream); G_src of shape (nd, Ns*SrcDim) is accumulated into."""
+        import torch
+        i = self.info
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if W_trg.dim() != 2 or W_trg.shape[1] != self.Nt * i["k1"]:
+            raise SctlAmdError("weights must have shape (nd, %d)" % (self.Nt * i["k1"]))
+        nd = W_trg.shape[0]
+        if G_src is None or tuple(G_src.shape) != (nd, self.Ns * i["k0"]):
+            G_src = torch.zeros((nd, self.Ns * i["k0"]), dtype=tdt, device=r_trg.device)
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        with torch.cuda.device(r_trg.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_lists_eval_transpose_densities_device(self._h, nd, _t_ptr(r_trg, tdt, self.Nt * 3, "r_trg"), _t_ptr(r_src, tdt, self.Ns * 3, "r_src"),
+                                                                        _t_ptr(n_src, tdt, self.Ns * i["nd"], "n_src"),
+                                                                        _t_ptr(W_trg, tdt, nd * self.Nt * i["k1"], "W_trg"),
+                                                                        _t_ptr(G_src, tdt, nd * self.Ns * i["k0"], "G_src"), digits, cp, cb,
+                                                                        C.c_void_p(st.cuda_stream)), "lists_eval_transpose_densities_device")
+        return G_src
+
     def close(self):
         if getattr(self, "_h", None):
             lib().sctl_amd_lists_destroy(self._h)
@@ -1174,3 +1217,27 @@ def eval_lists_transpose_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r
         return plan.eval_transpose_host(r_trg, r_src, n_src, w_trg, g_src, digits)
     finally:
         plan.close()
+
+
+def eval_lists_transpose_densities_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1, ctx=None, device=0):
+    """One-shot sctl_amd_eval_lists_transpose_densities_host: W_trg of shape (nd, Nt*TrgDim), returns (nd, Ns*SrcDim)."""
+    info = kernel_info(name)
+    dt = np.dtype(r_trg.dtype)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    W_trg = np.asarray(W_trg)
+    if W_trg.ndim != 2 or W_trg.shape[1] != Nt * info["k1"]:
+        raise SctlAmdError("weights must have shape (nd, %d)" % (Nt * info["k1"]))
+    nd = W_trg.shape[0]
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (trg_off, trg_cnt, src_off, src_cnt)]
+    if len({a.size for a in arrs}) != 1:
+        raise SctlAmdError("the four list arrays must have one entry per list")
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    if G_src is None or G_src.shape != (nd, Ns * info["k0"]):
+        G_src = np.zeros((nd, Ns * info["k0"]), dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    _check(lib().sctl_amd_eval_lists_transpose_densities_host(info["id"], _real_of(dt), nd, arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), Nt, Ns,
+                                                              _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                                              _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(W_trg, dt, nd * Nt * info["k1"], "W_trg"),
+                                                              _np_ptr(G_src, dt, nd * Ns * info["k0"], "G_src"), digits, cp, cb, device),
+           "eval_lists_transpose_densities_host")
+    return G_src

@@ -24,6 +24,11 @@ plan.eval_transpose_device; densities only.
     u = sctl_amd.autograd.lists_sum(plan, r_trg, r_src, None, v_src)
     u.square().sum().backward()                                                      # v_src.grad = sum over the lists of A_l^T (2 u)
 
+lists_sum_densities is lists_sum for several densities: the forward is plan.eval_densities_device, the backward
+plan.eval_transpose_densities_device, all gradient rows in one launch per pass; densities only.
+
+    U = sctl_amd.autograd.lists_sum_densities(plan, r_trg, r_src, None, V_src)       # V_src of shape (nd, Ns*SrcDim); U (nd, Nt*TrgDim)
+
 near_apply is NearOp.apply_device (the near-zone correction of a BoundaryIntegralOp, u = N f) with backward NearOp.apply_transpose_device;
 potential is DirectOp.eval_potential (ComputePotential: far field, weights, target normals and the attached near field; host tensors) with
 backward DirectOp.eval_potential_transpose.  Both differentiate the densities only.
@@ -159,6 +164,36 @@ def lists_sum(plan, r_trg, r_src, n_src, v_src, digits=-1):
         if t is not None and t.requires_grad:
             raise api.SctlAmdError("lists_sum differentiates with respect to the densities only: %s requires grad" % what)
     return _ListsSum.apply(plan, r_trg, r_src, n_src, v_src, digits)
+
+
+class _ListsSumDensities(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, plan, r_trg, r_src, n_src, V_src, digits):
+        fn_ctx.plan, fn_ctx.digits = plan, digits
+        fn_ctx.save_for_backward(r_trg, r_src, n_src)
+        return plan.eval_densities_device(r_trg.detach(), r_src.detach(), None if n_src is None else n_src.detach(), V_src.detach().contiguous(), digits=digits)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_U):
+        r_trg, r_src, n_src = fn_ctx.saved_tensors
+        g = None
+        if fn_ctx.needs_input_grad[4]:
+            g = fn_ctx.plan.eval_transpose_densities_device(r_trg, r_src, n_src, grad_U.contiguous(), digits=fn_ctx.digits)
+        return None, None, None, None, g, None
+
+
+def lists_sum_densities(plan, r_trg, r_src, n_src, V_src, digits=-1):
+    """plan.eval_densities_device on torch CUDA tensors (a fresh result of shape (nd, Nt*TrgDim)) that autograd can differentiate with respect to V_src,
+    of shape (nd, Ns*SrcDim): the backward is plan.eval_transpose_densities_device on the incoming gradient rows, on the forward's stream, as autograd
+    arranges, and is once-differentiable.  The plan must hold both directions."""
+    both = api.LISTS_FORWARD | api.LISTS_TRANSPOSE
+    if plan.directions != both:
+        raise api.SctlAmdError('lists_sum_densities needs a ListsPlan made with directions="both": the backward pass is the transposed list sum')
+    for what, t in (("r_trg", r_trg), ("r_src", r_src), ("n_src", n_src)):
+        if t is not None and t.requires_grad:
+            raise api.SctlAmdError("lists_sum_densities differentiates with respect to the densities only: %s requires grad" % what)
+    return _ListsSumDensities.apply(plan, r_trg, r_src, n_src, V_src, digits)
 
 
 class _NearApply(torch.autograd.Function):

@@ -3,6 +3,7 @@
 // whole waves), orders the work items by cost and keeps them on the device; an evaluation is ONE launch.
 #include "internal.hpp"
 #include "lists_multi_kernel.hpp"
+#include "lists_multi_transpose_kernel.hpp"
 #include "workspace.hpp"
 
 #include <algorithm>
@@ -593,6 +594,156 @@ int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nli
   int rc = sctl_amd_lists_create(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, &p);
   if (rc != SCTL_AMD_OK) return rc;
   rc = sctl_amd_lists_eval_densities_host(p, nd, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
+  sctl_amd_lists_destroy(p);
+  return rc;
+}
+
+// ---- several weight vectors through the transposed sum over the lists (sctl_amd_lists_eval_transpose_densities_*, lists_multi_transpose_kernel.hpp) ----
+// The plan is the single-vector transposed plan: the same handle serves any nd.
+}  // extern "C"
+
+namespace sctl_amd {
+namespace {
+// Launch table of the several-vectors transposed list forms: the built-in kernels only; a registered plugin kernel has none (null) and runs its
+// rows one at a time.
+const ListsMultiTEntry* ltmulti_entry(int kernel_id) {
+  static const ListsMultiTEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &ltmulti_Laplace3D_FxU(), &ltmulti_Laplace3D_DxU(), &ltmulti_Laplace3D_FxdU(),  &ltmulti_Stokes3D_FxU(),      &ltmulti_Stokes3D_DxU(),
+      &ltmulti_Stokes3D_FxT(),  &ltmulti_Stokes3D_FSxU(), &ltmulti_Stokes3D_FxUP(), &ltmulti_Laplace3D_FDxUdU(), &ltmulti_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+template <class R> ListsMultiTLaunch<R> ltmulti_launch(const ListsMultiTEntry& me, int mode, int form) {
+  if constexpr (std::is_same<R, double>::value) return me.f64[mode][form];
+  else return me.f32[mode][form];
+}
+// the form for `left` >= 2 rows still to do: the narrowest that takes them all, else the widest; -1: none (the single-vector kernel)
+template <class R> int ltmulti_form(const ListsMultiTEntry* me, int mode, int left) {
+  if (!me || left < 2) return -1;
+  int widest = -1;
+  for (int i = 0; i < kNumListMultiTM; i++) {
+    if (!ltmulti_launch<R>(*me, mode, i)) continue;
+    if (kListMultiTM[i] >= left) return i;
+    widest = i;
+  }
+  return widest;
+}
+
+int check_lists_transpose_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (const int rc = check_ctx(*p->k, ctx, ctx_bytes)) return rc;
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
+  return SCTL_AMD_OK;
+}
+
+// nd >= 2 weight vectors, row-major, on the plan's device: passes of the widest form, then the narrowest form that holds the rest; one row left
+// over (and every row of a plugin kernel) takes the single-vector transposed kernel on the same stream.  g is accumulated into.
+template <class R>
+int lists_eval_transpose_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* w, R* g, int digits, const void* ctx,
+                                     int ctx_bytes, hipStream_t st) {
+  const KernelEntry& k = *p->k;
+  const ListsSide& tr = p->side[1];
+  const int64_t w_stride = p->Nt * k.k1, g_stride = p->Ns * k.k0;
+  const ListsMultiTEntry* me = ltmulti_entry(k.id);
+  const int mode = mode_for(p->real, digits);
+  for (int m0 = 0; m0 < nd;) {
+    const int form = ltmulti_form<R>(me, mode, nd - m0);
+    if (form < 0) {
+      const int rc = sctl_amd_lists_eval_transpose_device(p, xt, xs, xn, w + m0 * w_stride, g + m0 * g_stride, digits, ctx, ctx_bytes, st);
+      if (rc) return rc;
+      m0++;
+      continue;
+    }
+    const int M = kListMultiTM[form], nact = nd - m0 < M ? nd - m0 : M;
+    (void)hipGetLastError();
+    ListMultiTArgs<R> a{};
+    a.l = ListTArgs<R>{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, xs, xn, xt, w + m0 * w_stride, g + m0 * g_stride,
+                       (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
+    std::memcpy(a.l.xcd_first, tr.xcd_first, sizeof a.l.xcd_first);
+    a.w_stride = w_stride; a.g_stride = g_stride; a.nact = nact;
+    ltmulti_launch<R>(*me, mode, form)(a, tr.nblocks, st);
+    LISTS_TRY(hipGetLastError());
+    count_work(tr.pairs * nact, k);
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+}  // namespace
+}  // namespace sctl_amd
+
+extern "C" {
+
+int sctl_amd_lists_eval_transpose_densities_device(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg,
+                                                   void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const int rc = check_lists_transpose_densities(p, nd, ctx, ctx_bytes);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_lists_eval_transpose_device(p, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes, stream);
+  if (nd == 0 || p->side[1].nitems == 0) return SCTL_AMD_OK;
+  if (!r_trg || !r_src || !w_trg || !g_src || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
+  DeviceScope scope(p->device);      // the work list lives on the plan's device
+  LISTS_TRY(scope.err);
+  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_transpose_densities_t<R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)w_trg, (R*)g_src, digits, ctx, ctx_bytes, (hipStream_t)stream); });
+}
+
+// Coordinates and normals go down once, the nd weight rows in one transfer, the nd result rows come back in one; the handle's device buffers
+// and pinned block are the single-vector entry's ([3] receives g_src, [4] holds w_trg), grown to nd rows on demand.
+int sctl_amd_lists_eval_transpose_densities_host(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg,
+                                                 void* g_src, int digits, const void* ctx, int ctx_bytes) {
+  const int rc0 = check_lists_transpose_densities(p, nd, ctx, ctx_bytes);
+  if (rc0) return rc0;
+  if (nd == 1) return sctl_amd_lists_eval_transpose_host(p, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes);
+  if (nd == 0 || p->side[1].nitems == 0) return SCTL_AMD_OK;
+  const KernelEntry& k = *p->k;
+  if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
+  const size_t rs = real_size(p->real);
+  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
+  const void* src[5] = {r_trg, r_src, n_src, nullptr, w_trg};
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  size_t total = 0;
+  for (int i = 0; i < 5; i++) {
+    total += Carver::pad(bytes[i]);
+    if (bytes[i] > p->dcap[i]) {
+      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
+      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
+      p->dcap[i] = bytes[i];
+    }
+  }
+  if (total > p->pinned_cap) {
+    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
+    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
+    p->pinned_cap = total;
+  }
+  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
+  const bool same = r_src == r_trg && bytes[0] == bytes[1];
+  Carver cut(p->pinned);
+  char* back = nullptr;
+  for (int i = 0; i < 5; i++) {
+    char* q = cut.take<char>(bytes[i]);
+    if (i == 3) { back = q; continue; }
+    if (!bytes[i] || (i == 1 && same)) continue;
+    std::memcpy(q, src[i], bytes[i]);
+    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
+  }
+  LISTS_TRY(hipMemsetAsync(p->dbuf[3], 0, bytes[3], p->st));
+  const int rc = sctl_amd_lists_eval_transpose_densities_device(p, nd, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[4], p->dbuf[3], digits, ctx,
+                                                                ctx_bytes, p->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[3], bytes[3], hipMemcpyDeviceToHost, p->st));
+  LISTS_TRY(hipStreamSynchronize(p->st));
+  add_into(p->real, g_src, back, (int64_t)nd * p->Ns * k.k0);      // g_src += device result, every row
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_eval_lists_transpose_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
+                                                 const int64_t* src_off, const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src,
+                                                 const void* n_src, const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, int device) {
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  sctl_amd_lists* p = nullptr;
+  int rc = sctl_amd_lists_create_directions(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, SCTL_AMD_LISTS_TRANSPOSE, &p);
+  if (rc != SCTL_AMD_OK) return rc;
+  rc = sctl_amd_lists_eval_transpose_densities_host(p, nd, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes);
   sctl_amd_lists_destroy(p);
   return rc;
 }
