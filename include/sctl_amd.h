@@ -245,8 +245,9 @@ int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, i
  * weight vectors per pass (4 for the traction kernel) on the exact all-pairs kernel (csrc/multi_transpose_kernel.hpp): sums in a fixed
  * order, bit-reproducible; a registered kernel with pair_t (which has no several-vectors form) is evaluated one row at a time on the same
  * stream, one without pair_t is SCTL_AMD_ERR_UNKNOWN_KERNEL.  fp32 runs this exact pair at every `digits`, as the single transposed entry
- * does.  Counters grow by nd*Nt*Ns pairs.  Not provided: several weight vectors over the P2P lists and any
- * multi-GPU form (the near field and the operator handle have theirs: sctl_amd_near_apply_transpose_densities_*). */
+ * does.  Counters grow by nd*Nt*Ns pairs.  Several weight vectors over the P2P lists:
+ * sctl_amd_lists_eval_transpose_densities_*; the near field and the operator handle have their forms too
+ * (sctl_amd_near_apply_transpose_densities_*, sctl_amd_op_eval_transpose_densities).  Not provided: an all-pairs multi-GPU form. */
 /* DEVICE arrays; enqueued on `stream`; g_src is accumulated into. */
 int sctl_amd_eval_transpose_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                                              const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream);
@@ -287,6 +288,34 @@ int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const 
  * streamed set into fewer splits. */
 int sctl_amd_eval_grad_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* trg_per_lane, int* trg_splits, int64_t* trg_workspace_bytes,
                             int* src_per_lane, int* src_splits, int64_t* src_workspace_bytes);
+
+/* ---- geometry gradients for several density / weight rows in one pass ---------------------------------------------------------------- */
+/* nd density rows v_src[m] and nd weight rows w_trg[m] on the same geometry: for L = sum_m <w_trg[m], A v_src[m]> — several incident fields, the six
+ * rigid motions of a body, the block of a block Krylov adjoint — the outputs are the SUMS over m of what nd calls of sctl_amd_eval_grad_* add,
+ *     g_trg (Nt x 3), g_src (Ns x 3), g_nrm (Ns x 3): one of each whatever nd is,
+ * with the work of a pair that does not depend on the rows (distance, reciprocal square root and its refinement, the powers of 1/r, d.n, Helmholtz's
+ * e^{ikr}) done once for several of them.  Layout is ROW-MAJOR as in sctl_amd_eval_densities_*: v_src is [nd][Ns*SrcDim], w_trg [nd][Nt*TrgDim].
+ * nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, and nd == 1 IS sctl_amd_eval_grad_* (bit-identical results, the same plan).  Everything
+ * else is as there: any output may be null and is then not computed, a pass none of whose outputs is asked for is not launched, g_nrm for a kernel
+ * without a normal is SCTL_AMD_ERR_BAD_ARGUMENT, argument errors come before any device work, Nt == 0 or Ns == 0 touches nothing.  The built-in
+ * kernels run up to 8 rows per pass (4 for the traction kernel) on csrc/multi_grad_kernel.hpp: sums in a fixed order, no atomics, bit-reproducible;
+ * a registered kernel with pair_g but no pair_gm is evaluated one row at a time into the same outputs on the same stream (exact: the outputs are
+ * sums), one without pair_g is SCTL_AMD_ERR_UNKNOWN_KERNEL.  Counters grow by nd*Nt*Ns pairs per side launched.  Not provided: the P2P lists, the near
+ * operator, the operator handle and any multi-GPU form. */
+/* DEVICE arrays; enqueued on `stream`; the outputs are accumulated into. */
+int sctl_amd_eval_grad_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                        const void* v_src, const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes,
+                                        void* stream);
+/* HOST arrays, one device; returns when the outputs are final.  accumulate != 0 adds to them, 0 overwrites them. */
+int sctl_amd_eval_grad_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                      const void* v_src, const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int accumulate, int digits, const void* ctx,
+                                      int ctx_bytes, int device);
+/* The plan of such a call (no side effects, no GPU needed): rows per pass of the widest pass and the number of passes (the last pass takes the
+ * narrowest form that holds what is left, one row the form of 2), and per side the splits of the streamed range of the first pass and the largest
+ * partial-sum workspace of one launch of any pass: [splits][owners * 3] (6 for the sources of a kernel with a normal), without a factor nd.  It stays
+ * within 2 GB as the single gradient's does, by cutting the owners into launches.  nd == 1 is sctl_amd_eval_grad_plan's answer. */
+int sctl_amd_eval_grad_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* rows_per_pass, int* passes, int* trg_splits,
+                                      int64_t* trg_workspace_bytes, int* src_splits, int64_t* src_workspace_bytes);
 
 /* ---- rank-parallel evaluation: one process per GPU (ParticleFMM::EvalDirect under MPI, fmm-wrapper.txx:504-561) --------------- */
 /* The reference partitions targets and sources over MPI ranks and rotates the source blocks round a ring (:537-558).  Here every

@@ -52,7 +52,9 @@
 // gets them: with phi = sum_k0 sum_k1 w[k1] U(d, n)[k0][k1] f[k0] it adds d phi / d d_j to G[j] and, where WANT_N, d phi / d n_j to N[j]; the same d, masking
 // rule and accuracy modes as pair(), plain f and w (no record).  It is called from both sides of the evaluator (targets own the sums / sources own them).  The sums
 // are taken as the derivative itself unless `static constexpr double grad_factor(int mode)` names the multiple pair_g accumulates.  Without pair_g the gradient
-// entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for the kernel and everything else runs as before.
+// entries answer SCTL_AMD_ERR_UNKNOWN_KERNEL for the kernel and everything else runs as before.  With pair_g a registered kernel also serves
+// sctl_amd_eval_grad_densities_* (several density / weight rows), one row at a time into the same outputs: the several-rows form pair_gm of the built-in functors
+// (ukernels.hpp, multi_grad_kernel.hpp) has no launch table in a plugin.
 // A kernel with per-launch constants of its own supplies a Consts type instead of DefaultConsts: it is built once per workgroup from
 // (double* lds) or, when it has such a constructor, from (double* lds, const KerCtx& ctx) — e.g. to derive scalar-register constants
 // from a wavenumber (ukernels.hpp: HelmholtzConsts) — and handed to every pair() call.

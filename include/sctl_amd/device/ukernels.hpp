@@ -41,6 +41,11 @@
 //                              rsqrt_masked<MODE, MASKED> (rsqrt_grad: fp32 always refined) (a gradient mixes the powers p and p + 2, and its owner holds no record a factor could be
 //                              folded into), so the sums need no per-mode factor.  A kernel that accumulates a multiple anyway names it in the
 //                              optional grad_factor(mode) (GradFactorOf; Helmholtz3D_FxU: its tables reduce the mode's C r).
+// and its form for M density / weight rows used by sctl_amd/csrc/multi_grad_kernel.hpp (optional, HasPairGM):
+//   pair_gm<R,MODE,MASKED[,VARIANT],WANT_N,M>(G, N, d, n, f, w, ctx, K)   f[M][K0], w[M][K1]: adds the derivatives of sum_m phi(f[m], w[m]).  Same d, root,
+//                              masking and grad_factor as pair_g; what does not depend on the rows is done once per pair.  phi is bilinear in (f, w), so the rows
+//                              are first contracted into the block C = sum_m f_m (x) w_m (contract_rows) and <U, C> is differentiated once — except the
+//                              traction kernel, whose rank-one terms run row by row (DESIGN.md §4.16 has the counts).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -248,6 +253,10 @@ template <class Ker, class R, int MODE> __device__ __forceinline__ void finish_t
 template <class Ker, class = void, class = void> struct HasPairG : std::false_type {};
 template <class Ker, class V> struct HasPairG<Ker, std::void_t<decltype(&Ker::template pair_g<double, 0, true, false>)>, V> : std::true_type {};
 template <class Ker> struct HasPairG<Ker, void, std::void_t<decltype(&Ker::template pair_g<double, 0, true, 0, false>)>> : std::true_type {};
+// ... and so is its form for several rows (pair_gm): a functor with pair_g alone has its rows evaluated one at a time
+template <class Ker, class = void, class = void> struct HasPairGM : std::false_type {};
+template <class Ker, class V> struct HasPairGM<Ker, std::void_t<decltype(&Ker::template pair_gm<double, 0, true, false, 2>)>, V> : std::true_type {};
+template <class Ker> struct HasPairGM<Ker, void, std::void_t<decltype(&Ker::template pair_gm<double, 0, true, 0, false, 2>)>> : std::true_type {};
 // pair_g of mode m accumulates GradFactorOf<Ker>::value(m) x the derivative: Ker::grad_factor(m) when named, else 1
 template <class Ker, class = void> struct GradFactorOf { static constexpr double value(int) { return 1; } };
 template <class Ker> struct GradFactorOf<Ker, std::void_t<decltype(Ker::grad_factor(0))>> { static constexpr double value(int mode) { return Ker::grad_factor(mode); } };
@@ -400,6 +409,38 @@ template <class R> __device__ __forceinline__ void stokeslet_grad(R (&G)[3], con
   for (int j = 0; j < 3; j++) G[j] = fma_(y3, fma_(B, f[j], fma_(A, w[j], -(c * d[j]))), G[j]);
 }
 
+// ---- gradient forms of several density / weight rows (pair_gm of every struct below) --------------------------------------------------------
+// Every phi is bilinear in (f, w), so the sum over rows of phi(f_m, w_m) is the single pair's form on the K0 x K1 block C = sum_m f_m (x) w_m:
+// C[a][b] += f[m][a] w[m][b] over the leading A x B corner of the rows, M FMAs per entry.
+template <int A, int B, class R, int M, int K0, int K1> __device__ __forceinline__ void contract_rows(R (&C)[A][B], const R (&f)[M][K0], const R (&w)[M][K1]) {
+#pragma unroll
+  for (int a = 0; a < A; a++)
+#pragma unroll
+    for (int b = 0; b < B; b++) {
+      R c = f[0][a] * w[0][b];
+#pragma unroll
+      for (int m = 1; m < M; m++) c = fma_(f[m][a], w[m][b], c);
+      C[a][b] = c;
+    }
+}
+// The Stokeslet family on the block C (and, for FSxU / FxUP, the 3-vector s of its extra row or column): phi = tr C y + (d^T C d + d.s) y^3, so with
+// u = (C + C^T) d, q = (d.u) / 2 + d.s:   grad phi = y^3 (u + s - d (tr C + 3 q y^2)).  EXTRA: there is an s (Stokes3D-FxU has none)
+template <bool EXTRA, class R> __device__ __forceinline__ void stokeslet_grad_c(R (&G)[3], const R (&d)[3], R y, const R (&C)[3][3], const R (&s)[3]) {
+  const R y2 = y * y, y3 = y2 * y;
+  R u[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) u[j] = fma_(C[j][2] + C[2][j], d[2], fma_(C[j][1] + C[1][j], d[1], (C[j][0] + C[0][j]) * d[0]));
+  R q = dot3(d, u) * R(0.5);
+  if constexpr (EXTRA) {
+    q += dot3(d, s);
+#pragma unroll
+    for (int j = 0; j < 3; j++) u[j] += s[j];
+  }
+  const R c = fma_(q * R(3), y2, (C[0][0] + C[1][1]) + C[2][2]);
+#pragma unroll
+  for (int j = 0; j < 3; j++) G[j] = fma_(y3, fma_(-c, d[j], u[j]), G[j]);
+}
+
 // ---- multi-density records (pack_m / pair_m of every struct below) -------------------------------------------------
 constexpr int nrec_multi(int nd, int k0, int m) { return (3 + nd + m * k0 + 1) / 2 * 2; }
 template <int ND, int K0, class R, int M> __device__ __forceinline__ void pack_multi(R* rec, const R* x, const R* n, const R (&f)[M][K0]) {
@@ -465,6 +506,15 @@ struct Laplace3D_FxU {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(-t, d[j], G[j]);
   }
+  // gradient, several rows: the scalar c = sum_m w_m f_m (M instructions), then pair_g with c for w f
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    R c[1][1];
+    contract_rows(c, f, w);
+    const R t = c[0][0] * ((y * y) * y);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(-t, d[j], G[j]);
+  }
 };
 
 // ---- Laplace double layer: u = (r.n) f / r^3   (kernel_functions.hpp:33-51); record holds n*f ------------
@@ -506,6 +556,21 @@ struct Laplace3D_DxU {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     const R y2 = y * y;
     const R a = (f[0] * w[0]) * (y2 * y);
+    const R b = (dot3(d, n) * R(-3)) * (y2 * a);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(a, n[j], fma_(b, d[j], G[j]));
+    if constexpr (WANT_N) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(a, d[j], N[j]);
+    }
+  }
+  // gradient, several rows: the scalar c = sum_m w_m f_m (M instructions), then pair_g with c for w f
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    R c[1][1];
+    contract_rows(c, f, w);
+    const R a = c[0][0] * (y2 * y);
     const R b = (dot3(d, n) * R(-3)) * (y2 * a);
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(a, n[j], fma_(b, d[j], G[j]));
@@ -565,6 +630,17 @@ struct Laplace3D_FxdU {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(a, w[j], fma_(b, d[j], G[j]));
   }
+  // gradient, several rows: the 3-vector v = sum_m f_m w_m (3 M instructions), then pair_g with f = 1 and w = v
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    R v[1][3];
+    contract_rows(v, f, w);
+    const R a = y2 * y;
+    const R b = (dot3(d, v[0]) * R(-3)) * (y2 * a);
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(a, v[0][j], fma_(b, d[j], G[j]));
+  }
 };
 
 // ---- Stokeslet: u_j = f_j / r + (r.f) r_j / r^3, scale 1/(8 pi)   (kernel_functions.hpp:74-95) -----------
@@ -615,6 +691,14 @@ struct Stokes3D_FxU {
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, dot3(d, f), dot3(d, w), dot3(f, w));
+  }
+  // gradient, several rows: the 3 x 3 block C = sum_m f_m (x) w_m (9 M instructions), then stokeslet_grad_c
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    R C[3][3];
+    contract_rows(C, f, w);
+    const R s[3] = {0, 0, 0};
+    stokeslet_grad_c<false>(G, d, y, C, s);
   }
 };
 
@@ -678,6 +762,27 @@ struct Stokes3D_DxU {
     for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(bc, n[j], fma_(ac, f[j], fma_(ab, w[j], e * d[j]))), G[j]);
     if constexpr (WANT_N) {
       const R t = bc * y5;
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(t, d[j], N[j]);
+    }
+  }
+  // gradient, several rows: the 3 x 3 block C = sum_m f_m (x) w_m (9 M instructions); phi = a q y^5 with a = d.n, q = d^T C d and u = (C + C^T) d = grad q:
+  //   grad_d = y^5 (q n + a u - 5 a q y^2 d), grad_n = q y^5 d
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    R C[3][3], u[3];
+    contract_rows(C, f, w);
+#pragma unroll
+    for (int j = 0; j < 3; j++) u[j] = fma_(C[j][2] + C[2][j], d[2], fma_(C[j][1] + C[1][j], d[1], (C[j][0] + C[0][j]) * d[0]));
+    const R q = dot3(d, u) * R(0.5);
+    const R a = dot3(d, n);
+    const R e = (a * q) * (y2 * R(-5));
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(q, n[j], fma_(a, u[j], e * d[j])), G[j]);
+    if constexpr (WANT_N) {
+      const R t = q * y5;
 #pragma unroll
       for (int j = 0; j < 3; j++) N[j] = fma_(t, d[j], N[j]);
     }
@@ -785,6 +890,29 @@ struct Stokes3D_FxT {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(q, f[j], fma_(A, v[j], e * d[j])), G[j]);
   }
+  // gradient, several rows: the rank-one terms row by row (the block f (x) w has 3 x 6 distinct entries: contracting it first costs about 21 M + 80
+  // instructions and 18 more registers against 29 M + 26 here: 164 against 142 at M = 4).  Per row v, q and A as in pair_g, summed unscaled; y^5 and
+  // y^2 applied once.
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    R H[3] = {0, 0, 0}, S = 0;
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+      R v[3];
+#pragma unroll
+      for (int j = 0; j < 3; j++) v[j] = fma_(w[m][j * 3 + 2] + w[m][6 + j], d[2], fma_(w[m][j * 3 + 1] + w[m][3 + j], d[1], (w[m][j * 3] + w[m][j]) * d[0]));
+      const R q = dot3(d, v) * R(0.5);
+      const R A = dot3(d, f[m]);
+      S = fma_(A, q, S);
+#pragma unroll
+      for (int j = 0; j < 3; j++) H[j] = fma_(q, f[m][j], fma_(A, v[j], H[j]));
+    }
+    const R e = S * (y2 * R(-5));
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(e, d[j], H[j]), G[j]);
+  }
 };
 
 // ---- Stokeslet + source/sink: u_j = f_j / r + ((r.f) + f_3) r_j / r^3   (kernel_functions.hpp:148-172) ------
@@ -853,6 +981,14 @@ struct Stokes3D_FSxU {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, fma_(d[2], f[2], fma_(d[1], f[1], fma_(d[0], f[0], f[3]))), dot3(d, w), dot3(w, f));
   }
+  // gradient, several rows: the 4 x 3 block C = sum_m f_m (x) w_m (12 M instructions); its last row is the source / sink's s (stokeslet_grad_c)
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    R C4[4][3];
+    contract_rows(C4, f, w);
+    const R C[3][3] = {{C4[0][0], C4[0][1], C4[0][2]}, {C4[1][0], C4[1][1], C4[1][2]}, {C4[2][0], C4[2][1], C4[2][2]}};
+    stokeslet_grad_c<true>(G, d, y, C, C4[3]);
+  }
 };
 
 // ---- velocity + pressure: Stokeslet and p = (r.f) / r^3   (kernel_functions.hpp:174-198) -------------------
@@ -920,6 +1056,15 @@ struct Stokes3D_FxUP {
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, dot3(d, f), fma_(d[2], w[2], fma_(d[1], w[1], fma_(d[0], w[0], w[3]))), dot3(f, w));
+  }
+  // gradient, several rows: the 3 x 4 block C = sum_m f_m (x) w_m (12 M instructions); its last column is the pressure's s (stokeslet_grad_c)
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    R C4[3][4];
+    contract_rows(C4, f, w);
+    const R C[3][3] = {{C4[0][0], C4[0][1], C4[0][2]}, {C4[1][0], C4[1][1], C4[1][2]}, {C4[2][0], C4[2][1], C4[2][2]}};
+    const R s[3] = {C4[0][3], C4[1][3], C4[2][3]};
+    stokeslet_grad_c<true>(G, d, y, C, s);
   }
 };
 
@@ -1050,6 +1195,32 @@ struct Laplace3D_FDxUdU {
       const R mu3 = mu * y3, e = fma_(h0, B, wu);
 #pragma unroll
       for (int j = 0; j < 3; j++) N[j] = fma_(mu3, fma_(e, d[j], wg[j]), N[j]);
+    }
+  }
+  // gradient, several rows: the 2 x 4 block C = sum_m (q, mu)_m (x) (w_u, w_g)_m (8 M instructions): c_q = C[0][0], c_m = C[1][0], the 3-vectors gq = C[0][1..3]
+  // and gm = C[1][1..3].  With dn = d.n, Bq = d.gq, Bm = d.gm the sums of pair_g's terms are
+  //   P3 = c_m dn + n.gm - Bq,    P5 = -3 dn Bm
+  //   grad_d = -y^3 (c_q + y^2 (3 P3 + 5 P5 y^2)) d + y^3 ((c_m - 3 y^2 Bm) n - 3 y^2 dn gm - gq)
+  //   grad_n = y^3 ((c_m - 3 y^2 Bm) d + gm)
+  template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y3 = y2 * y;
+    R C[2][4];
+    contract_rows(C, f, w);
+    const R* gq = C[0] + 1;
+    const R* gm = C[1] + 1;
+    const R dn = dot3(d, n), Bq = dot3(d, gq), Bm = dot3(d, gm), nw = dot3(n, gm);
+    const R h0 = -(y2 * K.c3);                               // -3 y^2
+    const R P3 = fma_(C[1][0], dn, nw) - Bq;
+    const R P5 = K.c3 * (-dn * Bm);
+    const R cd = -y3 * fma_(y2, fma_(P5 * R(5), y2, P3 * K.c3), C[0][0]);
+    const R cn = fma_(h0, Bm, C[1][0]), cw = h0 * dn;
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(cd, d[j], fma_(y3, fma_(cn, n[j], fma_(cw, gm[j], -gq[j])), G[j]));
+    if constexpr (WANT_N) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) N[j] = fma_(y3, fma_(cn, d[j], gm[j]), N[j]);
     }
   }
   template <class R, int MODE> static __device__ __forceinline__ void finish_t_mode(R (&acc)[K0]) { acc[0] *= R(rsqrt_scaled_c2(MODE)); }
@@ -1188,6 +1359,36 @@ struct Helmholtz3D_FxU {
     }
     const R y = rinv * R(K.cinv);
     const R cr = fma_(w[1], f[1], w[0] * f[0]), ci = fma_(-w[1], f[0], w[0] * f[1]);
+    const R hr = fma_(-ci, gi, cr * gr), hi = fma_(ci, gr, cr * gi);
+    const R a = REAL_K ? y : y + R(ctx.v[1]);
+    const R t = -fma_(R(ctx.v[0]), hi, a * hr) * y;
+#pragma unroll
+    for (int j = 0; j < 3; j++) G[j] = fma_(t, d[j], G[j]);
+  }
+  // gradient, several rows: the complex c = sum_m conj(w_m) f_m (4 M instructions), then pair_g's form on it; G and grad_factor as there
+  template <class R, int MODE, bool MASKED, int VARIANT, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&)[1], const R (&d)[3], const R (&)[1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+    const R y = rinv * R(K.cinv);
+    R cr = fma_(w[0][1], f[0][1], w[0][0] * f[0][0]), ci = fma_(-w[0][1], f[0][0], w[0][0] * f[0][1]);
+#pragma unroll
+    for (int m = 1; m < M; m++) {
+      cr = fma_(w[m][1], f[m][1], fma_(w[m][0], f[m][0], cr));
+      ci = fma_(-w[m][1], f[m][0], fma_(w[m][0], f[m][1], ci));
+    }
     const R hr = fma_(-ci, gi, cr * gr), hi = fma_(ci, gr, cr * gi);
     const R a = REAL_K ? y : y + R(ctx.v[1]);
     const R t = -fma_(R(ctx.v[0]), hi, a * hr) * y;

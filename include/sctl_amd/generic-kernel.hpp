@@ -314,6 +314,40 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_grad_host");
   }
 
+  // EvalGrad for several density / weight pairs in one evaluation (sctl_amd_eval_grad_densities_host; not in the reference): row m of F (nd x Ns*SrcDim)
+  // is a density, row m of W (nd x Nt*TrgDim) its target weights, and the outputs are the gradients of L = sum_m <W[m], A F[m]> — the sums over the rows of
+  // what EvalGrad adds, one g_trg, g_src and g_nrm whatever nd is — with the row-independent work of a pair done once for several rows.  The outputs follow
+  // EvalGrad's rule; F and W must have the same number of rows.  nd == 1 is EvalGrad's own path.
+  template <class Real, Integer digits = -1>
+  void EvalGradDensities(Vector<Real>* g_trg, Vector<Real>* g_src, Vector<Real>* g_nrm, const Vector<Real>& r_trg, const Vector<Real>& r_src,
+                         const Vector<Real>& n_src, const Matrix<Real>& F, const Matrix<Real>& W) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nd = F.Dim(0);
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(W.Dim(0) == nd);
+    SCTL_AMD_ASSERT(F.Dim(1) == Ns * KDIM0 || !nd);
+    SCTL_AMD_ASSERT(W.Dim(1) == Nt * KDIM1 || !nd);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(!g_nrm || N_DIM);
+    SCTL_AMD_ASSERT(nd <= 0x7fffffff);
+    auto size = [](Vector<Real>* g, Long n) {
+      if (g && g->Dim() != n) {
+        g->ReInit(n);
+        g->SetZero();
+      }
+    };
+    size(g_trg, Nt * DIM);
+    size(g_src, Ns * DIM);
+    size(g_nrm, Ns * DIM);
+    if (!nd) return;
+    RequireSupported();
+    const int rc = sctl_amd_eval_grad_densities_host(DeviceKernelId(), RealTag<Real>::value, (int)nd, Nt, Ns, r_trg.begin(), r_src.begin(),
+                                                     N_DIM ? n_src.begin() : nullptr, F.begin(), W.begin(), g_trg ? g_trg->begin() : nullptr,
+                                                     g_src ? g_src->begin() : nullptr, g_nrm ? g_nrm->begin() : nullptr, /*accumulate*/ 1, (int)digits, ctx_ptr,
+                                                     (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_grad_densities_host");
+  }
+
  private:
   static void RequireSupported() {
     if (!IsSupported()) {

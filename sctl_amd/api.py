@@ -39,7 +39,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_near_apply_transpose_host", "sctl_amd_near_apply_transpose_device", "sctl_amd_op_eval_transpose", "sctl_amd_op_eval_potential_transpose",
            "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan",
            "sctl_amd_near_apply_transpose_densities_host", "sctl_amd_near_apply_transpose_densities_device", "sctl_amd_op_eval_transpose_densities",
-           "sctl_amd_op_eval_potential_transpose_densities"]
+           "sctl_amd_op_eval_potential_transpose_densities",
+           "sctl_amd_eval_grad_densities_device", "sctl_amd_eval_grad_densities_host", "sctl_amd_eval_grad_densities_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -155,6 +156,9 @@ def lib():
     L.sctl_amd_eval_grad_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_grad_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_grad_plan.argtypes = [ci, ci, i64, i64, ci] + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)] * 2
+    L.sctl_amd_eval_grad_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_grad_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
+    L.sctl_amd_eval_grad_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_int), C.POINTER(i64)] * 2
     L.sctl_amd_near_apply_transpose_host.argtypes = [vp, vp, vp]
     L.sctl_amd_near_apply_transpose_device.argtypes = [vp, vp, vp, vp]
     L.sctl_amd_op_eval_transpose.argtypes = [vp, vp, vp, ci, ci, vp, ci]
@@ -282,6 +286,15 @@ def plan_grad(name, real, Nt, Ns, digits=-1):
     _check(lib().sctl_amd_eval_grad_plan(kernel_id(name), real, Nt, Ns, digits, *[C.byref(x) for x in v]), "eval_grad_plan")
     return dict(trg=dict(per_lane=v[0].value, splits=v[1].value, workspace_bytes=v[2].value),
                 src=dict(per_lane=v[3].value, splits=v[4].value, workspace_bytes=v[5].value))
+
+
+def plan_grad_densities(name, real, nd, Nt, Ns, digits=-1):
+    """Launch plan of a gradient evaluation of nd density / weight rows (sctl_amd_eval_grad_densities_plan): rows per pass of the widest pass, passes,
+    and per side ("trg", "src") the splits of the streamed range of the first pass and the largest partial-sum workspace of one launch."""
+    v = [C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_int(), C.c_int64()]
+    _check(lib().sctl_amd_eval_grad_densities_plan(kernel_id(name), real, nd, Nt, Ns, digits, *[C.byref(x) for x in v]), "eval_grad_densities_plan")
+    return dict(rows_per_pass=v[0].value, passes=v[1].value, trg=dict(splits=v[2].value, workspace_bytes=v[3].value),
+                src=dict(splits=v[4].value, workspace_bytes=v[5].value))
 
 
 def counters():
@@ -559,6 +572,64 @@ def eval_grad_device(name, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=
     return tuple(out)
 
 
+def _grad_rows(info, V_src, W_trg, Nt, Ns, dim):
+    """the number of rows of V_src (nd, Ns*SrcDim) and W_trg (nd, Nt*TrgDim)"""
+    if dim(V_src) != 2 or V_src.shape[1] != Ns * info["k0"]:
+        raise SctlAmdError("V_src must have shape (nd, %d)" % (Ns * info["k0"]))
+    if dim(W_trg) != 2 or W_trg.shape[1] != Nt * info["k1"]:
+        raise SctlAmdError("W_trg must have shape (nd, %d)" % (Nt * info["k1"]))
+    if V_src.shape[0] != W_trg.shape[0]:
+        raise SctlAmdError("V_src and W_trg must have the same number of rows, not %d and %d" % (V_src.shape[0], W_trg.shape[0]))
+    return V_src.shape[0]
+
+
+def eval_grad_densities_host(name, r_trg, r_src, n_src, V_src, W_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1, ctx=None, device=0,
+                             accumulate=True):
+    """Gradients of L = sum_m <W_trg[m], A V_src[m]> with respect to the target coordinates, the source coordinates and the source normals on host
+    (numpy) arrays (sctl_amd_eval_grad_densities_host): V_src of shape (nd, Ns*SrcDim), W_trg (nd, Nt*TrgDim); the outputs are the sums over the rows
+    of what eval_grad_host gives, one of each whatever nd is.  `want`, the outputs and `accumulate` are as there."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    nd = _grad_rows(info, V_src, W_trg, Nt, Ns, lambda a: a.ndim)
+    out = []
+    for wanted, g, n in zip(_grad_wanted(info, want), (g_trg, g_src, g_nrm), (Nt * 3, Ns * 3, Ns * 3)):
+        out.append(None if not wanted else g if g is not None and g.size == n else np.zeros(n, dtype=dt))
+    keep, cp, cb = _ctx_blob(info, ctx)
+    ptr = [None if g is None else _np_ptr(g, dt, g.size, what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+    _check(lib().sctl_amd_eval_grad_densities_host(info["id"], real, nd, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                                   _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(V_src, dt, nd * Ns * info["k0"], "V_src"),
+                                                   _np_ptr(W_trg, dt, nd * Nt * info["k1"], "W_trg"), ptr[0], ptr[1], ptr[2], 1 if accumulate else 0, digits,
+                                                   cp, cb, device), "eval_grad_densities_host")
+    return tuple(out)
+
+
+def eval_grad_densities_device(name, r_trg, r_src, n_src, V_src, W_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_grad_densities_device), enqueued on `stream` (default: torch's current stream); outputs of the
+    right size are accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    nd = _grad_rows(info, V_src, W_trg, Nt, Ns, lambda a: a.dim())
+    out = []
+    for wanted, g, n in zip(_grad_wanted(info, want), (g_trg, g_src, g_nrm), (Nt * 3, Ns * 3, Ns * 3)):
+        out.append(None if not wanted else g if g is not None and g.numel() == n else torch.zeros(n, dtype=tdt, device=r_trg.device))
+    keep, cp, cb = _ctx_blob(info, ctx)
+    ptr = [None if g is None else _t_ptr(g, tdt, g.numel(), what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_grad_densities_device(info["id"], real, nd, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                                         _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(V_src, tdt, nd * Ns * info["k0"], "V_src"),
+                                                         _t_ptr(W_trg, tdt, nd * Nt * info["k1"], "W_trg"), ptr[0], ptr[1], ptr[2], digits, cp, cb,
+                                                         C.c_void_p(st.cuda_stream)), "eval_grad_densities_device")
+    return tuple(out)
+
+
 def kernel_matrix_host(name, r_trg, r_src, n_src, digits=-1, ctx=None, device=0):
     """GenericKernel::KernelMatrix on numpy arrays: returns M of shape (Ns*SrcDim, Nt*TrgDim), scale included."""
     info = kernel_info(name)
@@ -661,6 +732,11 @@ class GenericKernel:
         if isinstance(r_trg, np.ndarray):
             return eval_grad_host(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
         return eval_grad_device(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
+
+    def EvalGradDensities(self, r_trg, r_src, n_src, V_src, W_trg, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
+        if isinstance(r_trg, np.ndarray):
+            return eval_grad_densities_host(self._info["id"], r_trg, r_src, n_src, V_src, W_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
+        return eval_grad_densities_device(self._info["id"], r_trg, r_src, n_src, V_src, W_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
 
     def KernelMatrix(self, M, Xt, Xs, Xn, digits=-1, **kw):
         if isinstance(Xt, np.ndarray):

@@ -17,6 +17,11 @@ sctl_amd_eval_transpose_densities_device, A^T (dloss/dU) for all rows in one pas
     U = sctl_amd.autograd.kernel_sum_densities("Stokes3D-FxUP", r_trg, r_src, None, V_src)    # V_src of shape (nd, Ns*SrcDim); U (nd, Nt*TrgDim)
     U.square().sum().backward()                                                      # V_src.grad[m] = A^T (2 U[m])
 
+kernel_sum_densities_geometry differentiates the geometry of such a block as well: its backward adds sctl_amd_eval_grad_densities_device, the
+gradients of sum_m <dloss/dU[m], A V_src[m]> for all rows in one pass.
+
+    U = sctl_amd.autograd.kernel_sum_densities_geometry("Stokes3D-DxU", r_trg, r_src, n_src, V_src)   # any of the four may require grad
+
 lists_sum is kernel_sum over the P2P lists of a ListsPlan made with directions="both": the forward is plan.eval_device, the backward
 plan.eval_transpose_device; densities only.
 
@@ -98,9 +103,45 @@ def kernel_sum_densities(name, r_trg, r_src, n_src, V_src, digits=-1, ctx=None):
     once-differentiable."""
     for what, t in (("r_trg", r_trg), ("r_src", r_src), ("n_src", n_src)):
         if t is not None and t.requires_grad:
-            raise api.SctlAmdError("kernel_sum_densities differentiates with respect to the densities only: %s requires grad; kernel_sum_geometry "
-                                   "differentiates coordinates and normals too" % what)
+            raise api.SctlAmdError("kernel_sum_densities differentiates with respect to the densities only: %s requires grad; "
+                                   "kernel_sum_densities_geometry differentiates coordinates and normals too" % what)
     return _KernelSumDensities.apply(name, r_trg, r_src, n_src, V_src, digits, ctx)
+
+
+class _KernelSumDensitiesGeometry(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, name, r_trg, r_src, n_src, V_src, digits, ctx):
+        fn_ctx.kernel = (name, digits, ctx)
+        r_trg, r_src, V_src = r_trg.detach().contiguous(), r_src.detach().contiguous(), V_src.detach().contiguous()
+        n_src = None if n_src is None else n_src.detach().contiguous()
+        fn_ctx.has_normal = n_src is not None
+        fn_ctx.shapes = (r_trg.shape, r_src.shape, None if n_src is None else n_src.shape)
+        fn_ctx.save_for_backward(*([r_trg, r_src, V_src] + ([n_src] if n_src is not None else [])))
+        return api.eval_densities_device(name, r_trg, r_src, n_src, V_src, digits=digits, ctx=ctx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_U):
+        name, digits, ctx = fn_ctx.kernel
+        r_trg, r_src, V_src = fn_ctx.saved_tensors[:3]
+        n_src = fn_ctx.saved_tensors[3] if fn_ctx.has_normal else None
+        grad_U = grad_U.contiguous()
+        need = fn_ctx.needs_input_grad
+        G_v = api.eval_transpose_densities_device(name, r_trg, r_src, n_src, grad_U, digits=digits, ctx=ctx) if need[4] else None
+        want = [what for what, i in (("trg", 1), ("src", 2), ("nrm", 3)) if need[i]]
+        g_trg = g_src = g_nrm = None
+        if want:
+            g = api.eval_grad_densities_device(name, r_trg, r_src, n_src, V_src, grad_U, want=want, digits=digits, ctx=ctx)
+            g_trg, g_src, g_nrm = [None if x is None else x.view(shape) for x, shape in zip(g, fn_ctx.shapes)]
+        return None, g_trg, g_src, g_nrm, G_v, None, None
+
+
+def kernel_sum_densities_geometry(name, r_trg, r_src, n_src, V_src, digits=-1, ctx=None):
+    """sctl_amd.eval_densities_device on torch CUDA tensors (a fresh result of shape (nd, Nt*TrgDim)) that autograd can differentiate with respect to
+    r_trg, r_src, n_src and V_src, of shape (nd, Ns*SrcDim): the backward is eval_transpose_densities_device for V_src and eval_grad_densities_device,
+    all rows in one pass, for whichever of the geometry tensors need a gradient.  It runs on the forward's stream, as autograd arranges, and is
+    once-differentiable."""
+    return _KernelSumDensitiesGeometry.apply(name, r_trg, r_src, n_src, V_src, digits, ctx)
 
 
 class _KernelSumGeometry(torch.autograd.Function):

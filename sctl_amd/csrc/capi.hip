@@ -153,6 +153,16 @@ int check_grad(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const voi
   if (!has_grad(*k)) return no_grad(*k);
   return SCTL_AMD_OK;
 }
+int check_grad_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                         const void* v_src, const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx) {
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of density and weight rows");
+  const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd > 0 && ((Ns > 0 && !v_src) || (Nt > 0 && !w_trg))) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or weight array");
+  if (g_nrm && k->nd == 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string(k->name) + " has no source normal: g_nrm must be null");
+  if (!has_grad(*k)) return no_grad(*k);
+  return SCTL_AMD_OK;
+}
 }  // namespace sctl_amd
 
 using namespace sctl_amd;
@@ -446,6 +456,58 @@ int sctl_amd_eval_grad_plan(int kernel, int real, int64_t Nt, int64_t Ns, int di
   if (src_per_lane) *src_per_lane = k->grad_t[1];
   if (src_splits) *src_splits = ps.splits;
   if (src_workspace_bytes) *src_workspace_bytes = ps.workspace_bytes;
+  return SCTL_AMD_OK;
+}
+
+// ---- the same for several density / weight rows: the gradients of sum_m <w_trg[m], A v_src[m]> -------------------------------------------------
+// nd == 1 goes through the single gradient entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+int sctl_amd_eval_grad_densities_device(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                        const void* v_src, const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes,
+                                        void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_grad_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_nrm, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_grad_device(kernel, real, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits, ctx, ctx_bytes, stream);
+  if (device_count_quiet() <= 0) return no_device();
+  return eval_grad_densities_device(*k, real, nd, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_grad_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* rows_per_pass, int* passes, int* trg_splits,
+                                      int64_t* trg_workspace_bytes, int* src_splits, int64_t* src_workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (const int rc = check_real_sizes(k, real, Nt, Ns)) return rc;
+  if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of density and weight rows");
+  if (!has_grad(*k)) return no_grad(*k);
+  (void)digits;   // every accuracy mode runs the same launch geometry
+  int rpp = 0, np = 0, s[2] = {0, 0};
+  int64_t ws[2] = {0, 0};
+  const MultiGEntry* me = multi_g_entry(k->id);
+  if (nd == 1 || (nd > 1 && !me)) {   // the single gradient plan, once per row
+    rpp = 1; np = nd;
+    for (int side = 0; side < 2; side++) {
+      const PlanOwned p = make_plan_g(*k, real, side, Nt, Ns);
+      s[side] = p.splits; ws[side] = p.workspace_bytes;
+    }
+  } else if (nd > 1) {
+    // the first pass is the widest; the workspace is the largest any pass asks for
+    for (int m0 = 0; m0 < nd;) {
+      const int left = nd - m0, M = kMultiGM[multi_g_form(*me, left)];
+      for (int side = 0; side < 2; side++) {
+        const PlanOwned p = make_plan_gm(*k, M, real, side, Nt, Ns);
+        if (np == 0) s[side] = p.splits;
+        ws[side] = p.workspace_bytes > ws[side] ? p.workspace_bytes : ws[side];
+      }
+      if (np == 0) rpp = M;
+      np++;
+      m0 += left < M ? left : M;
+    }
+  }
+  if (rows_per_pass) *rows_per_pass = rpp;
+  if (passes) *passes = np;
+  if (trg_splits) *trg_splits = s[0];
+  if (trg_workspace_bytes) *trg_workspace_bytes = ws[0];
+  if (src_splits) *src_splits = s[1];
+  if (src_workspace_bytes) *src_workspace_bytes = ws[1];
   return SCTL_AMD_OK;
 }
 

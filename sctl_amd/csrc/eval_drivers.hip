@@ -1,6 +1,6 @@
 // Launch planning and the typed launch drivers of the all-pairs evaluators, behind the untyped functions of eval_drivers.hpp: the forward sum, several
 // densities, the transposed sum, several weight vectors through it, the geometry gradients and the kernel matrix.  All arithmetic lives in eval_kernel.hpp /
-// multi_kernel.hpp / multi_transpose_kernel.hpp / ukernels.hpp.
+// multi_kernel.hpp / multi_transpose_kernel.hpp / multi_grad_kernel.hpp / ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -144,6 +144,19 @@ PlanOwned make_plan_g(const KernelEntry& k, int real, int side, int64_t Nt, int6
   const int64_t rs = (int64_t)real_size(real);
   if (side == 0) return plan_owned(Nt, Ns, k.grad_t[0], 3 + k.nd + k.k0, 3, rs);
   return plan_owned(Ns, Nt, k.grad_t[1], 3 + k.k1, grad_out_width(k, 1), rs);
+}
+PlanOwned make_plan_gm(const KernelEntry& k, int M, int real, int side, int64_t Nt, int64_t Ns) {
+  const int64_t rs = (int64_t)real_size(real), owners = side == 0 ? Nt : Ns, width = grad_out_width(k, side);
+  PlanOwned p = side == 0 ? plan_owned(Nt, Ns, 1, 3 + k.nd + (int64_t)M * k.k0, width, rs) : plan_owned(Ns, Nt, 1, 3 + (int64_t)M * k.k1, width, rs);
+  if (p.splits >= 8 && (p.splits & 7)) {   // in eights (the splits past the streamed set have no work): the XCD-owned mapping; the owner cut follows
+    p.splits = (p.splits + 7) / 8 * 8;
+    int64_t cap = transpose_workspace_cap() / ((int64_t)p.splits * width * rs) / kBlock * kBlock;
+    if (cap < kBlock) cap = kBlock;
+    p.owners_per_launch = owners > 0 ? owners : 1;
+    if (p.owners_per_launch > cap) p.owners_per_launch = cap;
+    p.workspace_bytes = (int64_t)p.splits * p.owners_per_launch * width * rs;
+  }
+  return p;
 }
 
 // Tile-centred fast path (centered_kernel.hpp): Laplace single layer (fp64 and fp32) on problems large enough to amortise the
@@ -543,6 +556,94 @@ int eval_transpose_densities_device_t(const KernelEntry& k, int real, int nd, in
 }
 }  // namespace
 
+// ---- geometry gradients for several density / weight rows (sctl_amd_eval_grad_densities_*, multi_grad_kernel.hpp) ------------------------------
+const MultiGEntry* multi_g_entry(int kernel_id) {
+  static const MultiGEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &multi_g_Laplace3D_FxU(), &multi_g_Laplace3D_DxU(), &multi_g_Laplace3D_FxdU(),  &multi_g_Stokes3D_FxU(),      &multi_g_Stokes3D_DxU(),
+      &multi_g_Stokes3D_FxT(),  &multi_g_Stokes3D_FSxU(), &multi_g_Stokes3D_FxUP(), &multi_g_Laplace3D_FDxUdU(), &multi_g_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+int multi_g_form(const MultiGEntry& me, int left) {
+  for (int i = 0; i < kNumMultiGM; i++)
+    if (kMultiGM[i] >= left || kMultiGM[i] == me.m_max) return i;
+  return 0;
+}
+
+namespace {
+// One side of one pass of `nact` rows on the form of kMultiGM[form] rows.  A form that is not in the table is served by the single kernel, one row at a time
+// into the same outputs.
+template <class R>
+int eval_grad_multi_side(const KernelEntry& k, const MultiGEntry& me, int form, int real, int side, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn,
+                         const R* f, const R* w, int nact, R* g, R* gn, int mode, const void* ctx, hipStream_t st) {
+  const int64_t f_stride = Ns * k.k0, w_stride = Nt * k.k1;
+  MultiGLaunch<R> launch;
+  if constexpr (std::is_same<R, double>::value) launch = me.f64[mode][side][form];
+  else launch = me.f32[mode][side][form];
+  if (!launch) {
+    for (int m = 0; m < nact; m++)
+      if (const int rc = eval_grad_side<R>(k, real, side, Nt, Ns, xt, xs, xn, f + m * f_stride, w + m * w_stride, g, gn, mode, ctx, st)) return rc;
+    return SCTL_AMD_OK;
+  }
+  const PlanOwned p = make_plan_gm(k, kMultiGM[form], real, side, Nt, Ns);
+  const R scale = (R)(k.scale / k.grad_factor[mode]);
+  const int64_t owners = side == 0 ? Nt : Ns;
+  const bool normal = (side == 1 && k.nd > 0);
+  void* ws = nullptr;
+  if (p.splits > 1) HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+  for (int64_t o0 = 0; o0 < owners; o0 += p.owners_per_launch) {   // one launch unless the partial sums of all owners would pass 2 GB
+    const int64_t n = (owners - o0 < p.owners_per_launch) ? owners - o0 : p.owners_per_launch;
+    MultiGArgs<R> a{};
+    a.No = n; a.partial = (R*)ws; a.chunk = p.chunk; a.nact = nact; a.scale = scale; a.ctx = make_ctx(k, ctx);
+    a.f_stride = f_stride; a.w_stride = w_stride;
+    a.g = g ? g + o0 * 3 : nullptr;
+    a.gn = (normal && gn) ? gn + o0 * 3 : nullptr;
+    if (side == 0) { a.Nst = Ns; a.xo = xt + o0 * 3; a.xst = xs; a.xn = xn; a.f = f; a.w = w + o0 * k.k1; }
+    else { a.Nst = Nt; a.xo = xs + o0 * 3; a.xst = xt; a.xn = xn ? xn + o0 * k.nd : nullptr; a.f = f + o0 * k.k0; a.w = w; }
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)p.splits);
+    launch(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (p.splits > 1) {
+      const int64_t m = n * 3;
+      const dim3 rgrid((unsigned)((m + kBlock - 1) / kBlock));
+      if (a.g) hipLaunchKernelGGL((reduce_splits_kernel<R>), rgrid, dim3(kBlock), 0, st, a.g, (const R*)a.partial, m, p.splits, scale);
+      if (a.gn) hipLaunchKernelGGL((reduce_splits_kernel<R>), rgrid, dim3(kBlock), 0, st, a.gn, (const R*)a.partial + (int64_t)p.splits * m, m, p.splits, scale);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  count_work((int64_t)nact * Nt * Ns, k);
+  return SCTL_AMD_OK;
+}
+
+// nd >= 2 rows, row-major, on the device: passes of the widest form, the last pass on the narrowest form that takes what is left, every pass accumulating
+// into the same outputs.  A plugin kernel with pair_g has no pair_gm: its rows go one at a time through the single path, which is exact (the outputs are sums).
+template <class R>
+int eval_grad_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, const R* w,
+                                 R* g_trg, R* g_src, R* g_nrm, int digits, const void* ctx, hipStream_t st) {
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
+  const int64_t f_stride = Ns * k.k0, w_stride = Nt * k.k1;
+  const MultiGEntry* me = multi_g_entry(k.id);
+  const int mode = mode_for(real, digits);
+  for (int m0 = 0; m0 < nd;) {
+    const R* fm = f + m0 * f_stride;
+    const R* wm = w + m0 * w_stride;
+    if (!me) {
+      if (const int rc = eval_grad_device_t<R>(k, real, Nt, Ns, xt, xs, xn, fm, wm, g_trg, g_src, g_nrm, digits, ctx, st)) return rc;
+      m0++;
+      continue;
+    }
+    (void)hipGetLastError();
+    const int left = nd - m0, form = multi_g_form(*me, left);
+    const int nact = left < kMultiGM[form] ? left : kMultiGM[form];
+    if (g_trg)
+      if (const int rc = eval_grad_multi_side<R>(k, *me, form, real, 0, Nt, Ns, xt, xs, xn, fm, wm, nact, g_trg, nullptr, mode, ctx, st)) return rc;
+    if (g_src || g_nrm)
+      if (const int rc = eval_grad_multi_side<R>(k, *me, form, real, 1, Nt, Ns, xt, xs, xn, fm, wm, nact, g_src, g_nrm, mode, ctx, st)) return rc;
+    m0 += nact;
+  }
+  return SCTL_AMD_OK;
+}
+}  // namespace
+
 // ---- the untyped seam: `real` picks the template here and nowhere else ----------------------------------------------------------------------------
 int eval_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, void* v, int digits,
                 const void* ctx, hipStream_t st, int64_t nt_whole, bool presorted) {
@@ -563,6 +664,10 @@ int eval_transpose_densities_device(const KernelEntry& k, int real, int nd, int6
 int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* w,
                      void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st) {
   return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_grad_device_t<R>(k, real, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)f, (const R*)w, (R*)g_trg, (R*)g_src, (R*)g_nrm, digits, ctx, st); });
+}
+int eval_grad_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f,
+                               const void* w, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st) {
+  return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_grad_densities_device_t<R>(k, real, nd, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)f, (const R*)w, (R*)g_trg, (R*)g_src, (R*)g_nrm, digits, ctx, st); });
 }
 int matrix_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, void* M, int digits, const void* ctx,
                   hipStream_t st) {

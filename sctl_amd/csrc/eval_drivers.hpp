@@ -4,6 +4,7 @@
 #include "internal.hpp"
 #include "multi_kernel.hpp"
 #include "multi_transpose_kernel.hpp"
+#include "multi_grad_kernel.hpp"
 
 namespace sctl_amd {
 // centered.hip
@@ -71,6 +72,14 @@ struct MultiTPlan {
 };
 MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int form, int real, int64_t Nt, int64_t Ns);
 
+// ---- geometry gradients for several density / weight rows (multi_grad_kernel.hpp) ----
+const MultiGEntry* multi_g_entry(int kernel_id);    // null for a registered plugin kernel: its rows go one at a time through the single gradient path
+int multi_g_form(const MultiGEntry& me, int left);  // as multi_form
+// make_plan_g with M rows in a streamed record: plan_owned with one owner per lane, the L2 rule counting all M rows in a split's streamed bytes, and the
+// splits in eights from 8 on.  The partial sums are [splits][owners * 3] (6 with a normal) whatever M is: the bound and its lowering variable are the
+// single gradient's.
+PlanOwned make_plan_gm(const KernelEntry& k, int M, int real, int side, int64_t Nt, int64_t Ns);
+
 // ---- the tile-centred fast path (centered.hip) ----
 // mode < 0: the mode of the default accuracy request (what an operator handle sorts its targets for)
 bool has_centered_path(const KernelEntry& k, int real, int mode = -1);
@@ -100,6 +109,10 @@ int eval_transpose_densities_device(const KernelEntry& k, int real, int nd, int6
 // not computed, and a side whose outputs are all null is not launched
 int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* w,
                      void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st);
+// nd >= 2 density and weight rows, row-major: the outputs += the gradients of sum_m <w[m], A f[m]> (a single row must take eval_grad_device: this one
+// would run it on the form of 2)
+int eval_grad_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f,
+                               const void* w, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st);
 int matrix_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, void* M, int digits, const void* ctx,
                   hipStream_t st);
 void matrix_batch_launch(const KernelEntry& k, int real, const MatTile* tiles, int64_t ntiles, const void* xt, const void* xs, const void* xn, void* M,

@@ -1,0 +1,8 @@
+// Gradient forms of Stokes3D_FSxU for several density / weight rows (multi_grad_kernel.hpp): forms of 2 .. 8 rows, both sides.
+#include "multi_grad_kernel.hpp"
+namespace sctl_amd {
+const MultiGEntry& multi_g_Stokes3D_FSxU() {
+  static const MultiGEntry e = make_multi_g_entry<Stokes3D_FSxU, 8>();
+  return e;
+}
+}  // namespace sctl_amd

@@ -251,6 +251,34 @@ int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const 
   return rc ? rc : c.finish();
 }
 
+// nd == 1 goes through the single gradient entry (bit-identical results); nd == 0 is a no-op after the argument checks.
+// Coordinates and normals go down once, the nd density rows and the nd weight rows in one transfer each; the outputs do not grow with nd.
+int sctl_amd_eval_grad_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                      const void* v_src, const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int accumulate, int digits, const void* ctx,
+                                      int ctx_bytes, int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_grad_densities(k, real, nd, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_nrm, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (nd == 1) return sctl_amd_eval_grad_host(kernel, real, Nt, Ns, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, accumulate, digits, ctx, ctx_bytes, device);
+  if ((rc = check_device(device))) return rc;
+  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;   // nothing is read or written
+  const size_t rs = real_size(real);
+  HostCall c(device, real);
+  c.in(0, r_trg, (size_t)Nt * 3 * rs);
+  c.in(1, r_src, (size_t)Ns * 3 * rs);
+  c.in(2, n_src, (size_t)Ns * k->nd * rs);
+  c.in(3, v_src, (size_t)nd * Ns * k->k0 * rs);
+  c.in(4, w_trg, (size_t)nd * Nt * k->k1 * rs);
+  void* out[3] = {g_trg, g_src, g_nrm};   // a null output is not declared: no buffer, no transfer
+  for (int i = 0; i < 3; i++)
+    if (out[i]) c.out(5 + i, out[i], (size_t)(i == 0 ? Nt : Ns) * 3 * rs, HostCall::kZero | HostCall::kStaged | (accumulate ? HostCall::kAccumulate : 0));
+  rc = c.start();
+  if (rc == SCTL_AMD_OK)
+    rc = eval_grad_densities_device(*k, real, nd, Nt, Ns, c.dev(0), c.dev(1), k->nd ? c.dev(2) : nullptr, c.dev(3), c.dev(4), g_trg ? c.dev(5) : nullptr,
+                                    g_src ? c.dev(6) : nullptr, g_nrm ? c.dev(7) : nullptr, digits, ctx, c.st);
+  return rc ? rc : c.finish();
+}
+
 int sctl_amd_kernel_matrix_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, void* M,
                                 int digits, const void* ctx, int ctx_bytes, int device) {
   const KernelEntry* k = registry(kernel);

@@ -45,7 +45,9 @@ int check_transpose_densities(const KernelEntry* k, int real, int nd, int64_t Nt
                               const void* w_trg, const void* g_src, int ctx_bytes, const void* ctx);
 int check_grad(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
                const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx);
-int no_device();                                   // SCTL_AMD_ERR_NO_DEVICE with the text every entry gives
+int check_grad_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                         const void* v_src, const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx);
+int no_device();                                  // SCTL_AMD_ERR_NO_DEVICE with the text every entry gives
 int check_device(int device);                      // ... and a device index within the devices there are
 
 struct HipPinned {
