@@ -1,6 +1,7 @@
 // Host driver of the tile-centred Laplace single-layer path (centered_kernel.hpp): sort the targets along the Hilbert curve on the device
 // (curve_key.hpp; rocPRIM radix sort of 63-bit keys), evaluate on the sorted order, scatter-add the result back.  Everything is enqueued
 // on the caller's stream; temporaries are carved out of the stream's scratch block (workspace.hpp).
+// The fp64 single layer first groups its sources by the sign of the density, once per launch (fold_prepass.hpp; the records lie next to the partial sums).
 #include "centered_kernel.hpp"
 #include "centered_mfma_kernel.hpp"
 #include <sctl_amd/device/launch.hpp>
@@ -125,6 +126,12 @@ void centered_plan(int64_t Nt, int64_t Ns, int cus, int src_bytes, int out_bytes
   *splits = (int)((Ns + *chunk - 1) / *chunk);
 }
 
+// The pre-pass of a launch of the folding kernel into `blk` (FoldPrepLayout(splits, chunk).bytes of scratch); what the kernel takes as a.xn
+template <class R> const R* fold_prepass(const R* xs, const R* f, int64_t Ns, int splits, int64_t chunk, char* blk, hipStream_t st) {
+  if constexpr (std::is_same<R, double>::value) hipLaunchKernelGGL(fold_prepass_kernel, dim3((unsigned)splits), dim3(kFoldPrepBlock), 0, st, xs, f, Ns, chunk, blk);
+  return (const R*)blk;
+}
+
 template <class CP, class R>
 hipError_t eval_centered_t(int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, R* v_trg, double scale_d, int mode, int cus,
                            hipStream_t st, bool presorted, int64_t density) {
@@ -133,17 +140,24 @@ hipError_t eval_centered_t(int64_t Nt, int64_t Ns, const R* xt, const R* xs, con
   int T, splits;
   int64_t chunk;
   centered_plan(Nt, Ns, cus, (int)sizeof(R) * (3 + CP::Ker::ND + CP::Ker::K0), (int)sizeof(R) * K1, &T, &splits, &chunk);
+  // the fp64 single layer reads its sources as the records of a pre-pass over this launch's densities (fold_prepass.hpp), next to the partial sums
+  constexpr bool FOLD = FoldsDensity<CP>::value && std::is_same<R, double>::value;
+  const size_t prep_bytes = FOLD ? (size_t)FoldPrepLayout(splits, chunk).bytes : 0;
   if (presorted) {   // the caller keeps the targets in Morton order (sctl_amd_op_*): no sort, no gather, results in place
     R* partial = nullptr;
-    if (splits > 1) {
-      void* base = nullptr;
-      CENTERED_TRY(workspace_acquire(st, sizeof(R) * (size_t)splits * (size_t)Nt * K1, &base));
-      partial = (R*)base;
-    }
+    const size_t partial_bytes = (splits > 1) ? Carver::pad(sizeof(R) * (size_t)splits * (size_t)Nt * K1) : 0;
     EvalArgs<R> a{};
-    a.Nt = Nt; a.Ns = Ns; a.xt = xt; a.xs = xs; a.xn = xn; a.f = f; a.v_trg = v_trg; a.partial = partial;
+    a.Nt = Nt; a.Ns = Ns; a.xt = xt; a.xs = xs; a.xn = xn; a.f = f; a.v_trg = v_trg;
     a.chunk = chunk; a.scale = scale;
     a.ctx.v[0] = kNearFactor2;
+    if (partial_bytes + prep_bytes > 0) {
+      void* base = nullptr;
+      CENTERED_TRY(workspace_acquire(st, partial_bytes + prep_bytes, &base));
+      Carver cut(base);
+      if (splits > 1) partial = cut.take<R>((size_t)splits * (size_t)Nt * K1);
+      if constexpr (FOLD) a.xn = fold_prepass(xs, f, Ns, splits, chunk, cut.take<char>(prep_bytes), st);
+    }
+    a.partial = partial;
     const int64_t per_wave = centered_targets_per_wave(CP::Ker::ID, sizeof(R) == 8 ? 0 : 1, mode, density);
     const dim3 grid((unsigned)((Nt + per_wave - 1) / per_wave), (unsigned)splits);
     if (mode == 0) launch_centered<CP, R, 0>(a, grid, (int)per_wave, st);
@@ -162,7 +176,7 @@ hipError_t eval_centered_t(int64_t Nt, int64_t Ns, const R* xt, const R* xs, con
   const size_t n = (size_t)Nt;
   const size_t total = Carver::pad(sizeof(double) * 6 * nblk_box) + 2 * Carver::pad(sizeof(uint64_t) * n) + 2 * Carver::pad(sizeof(uint32_t) * n) +
                        Carver::pad(sizeof(R) * 3 * n) + Carver::pad(sizeof(R) * n * K1) + Carver::pad(tmp_bytes) +
-                       (splits > 1 ? Carver::pad(sizeof(R) * (size_t)splits * n * K1) : 0);
+                       (splits > 1 ? Carver::pad(sizeof(R) * (size_t)splits * n * K1) : 0) + prep_bytes;
   void* base = nullptr;
   CENTERED_TRY(workspace_acquire(st, total, &base));
   Carver cut(base);
@@ -185,6 +199,7 @@ hipError_t eval_centered_t(int64_t Nt, int64_t Ns, const R* xt, const R* xs, con
   a.chunk = chunk; a.scale = scale;
   a.ctx.v[0] = kNearFactor2;
   a.partial = partial;
+  if constexpr (FOLD) a.xn = fold_prepass(xs, f, Ns, splits, chunk, cut.take<char>(prep_bytes), st);
   const int64_t per_wave = centered_targets_per_wave(CP::Ker::ID, sizeof(R) == 8 ? 0 : 1, mode, density);
   const dim3 grid((unsigned)((Nt + per_wave - 1) / per_wave), (unsigned)splits);
   if (mode == 0) launch_centered<CP, R, 0>(a, grid, (int)per_wave, st);

@@ -19,6 +19,7 @@
 #pragma once
 #include <sctl_amd/device/eval_kernel.hpp>
 #include "curve_key.hpp"
+#include "fold_prepass.hpp"
 
 namespace sctl_amd {
 
@@ -158,19 +159,13 @@ template <class R> struct CenteredFxU {      // u += f / r
   // and the seed rsq(r2') = |f| / r.  The refinement is scale-invariant (rsqrt_scaled_split), so y0 P = C |f| / r and the pair ends in
   // acc = fma(+-y0, P, acc): the product by the density and the refinement's last product are one instruction — 8 fp64 instructions + v_rsq_f64
   // per far pair at full precision where the unfolded pair takes 9 + v_rsq_f64.  The sign of f is not in the record: the kernel keeps the far
-  // sources of either sign in a list of their own (FOLD) and subtracts the negative ones (the FMA's neg modifier).  Sources the fold cannot take
-  // go elsewhere (fold_class).
+  // sources of either sign in a list of their own (FOLD) and subtracts the negative ones (the FMA's neg modifier).  Which sign, k itself, and
+  // the sources the fold cannot take for any centre (f == 0: dropped; f not finite or k out of every band: the exact pair, so that NaN and inf
+  // propagate as in the reference) are decided once per launch by the source pre-pass (fold_prepass.hpp, fold_prepass_kernel); the kernel keeps the
+  // test that depends on the wave's centre — a scaled record out of the safe range takes the exact pair too: the terms of r2' are at most
+  // ~2.5 k |x_s'|^2 (a far source has r^2 >= |x_s'|^2 / 4), and |k x_s'| = k |x_s'|^2 / |x_s'| <= 2^750 with the bands k |x_s'|^2 in
+  // [2^-600, 2^600] and |x_s'|^2 in [2^-300, 2^300].
   static constexpr bool FOLD = !DUP;
-  // 1: positive far list, -1: negative far list, 0: f == 0, contributes exactly 0 (dropped), 2: the exact pair — f not finite (NaN and inf propagate
-  // as in the reference), or a scaled record out of the safe range: the terms of r2' are at most ~2.5 k |x_s'|^2 (a far source has r^2 >= |x_s'|^2 / 4),
-  // and |k x_s'| = k |x_s'|^2 / |x_s'| <= 2^750 with the two bands below
-  static __device__ __forceinline__ int fold_class(R f, R ss, R& k) {
-    if (f == R(0)) return 0;
-    k = R(1) / (f * f);   // f * f over- or underflows to inf or 0 for |f| beyond ~1e+-154: k ss is then 0 or inf, out of the band
-    const R kss = k * ss;
-    if (!(kss >= R(0x1p-600) && kss <= R(0x1p600) && ss >= R(0x1p-300) && ss <= R(0x1p300))) return 2;
-    return f > R(0) ? 1 : -1;
-  }
   static __device__ __forceinline__ void put_folded(typename Rec4<R>::V* rec, R* base, int q, const R (&p)[3], R ss, R k) {
     Rec4<R>::put(rec + q * Rec4<R>::NW, k * p[0], k * p[1], k * p[2], k * ss);
     base[q] = k;
@@ -364,11 +359,12 @@ __device__ __forceinline__ void centered_tile_and_split(unsigned& tile_idx, unsi
     split_idx = xcd * per + j / gridDim.x;
   }
 }
-// whether a policy folds the density into its far records (CenteredFxU<double>::FOLD): two far lists by the sign of the density
+// whether a policy folds the density into its far records (CenteredFxU<double>::FOLD): sources from the pre-pass, two far lists by the sign of the density
 template <class CP, class = void> struct FoldsDensity : std::false_type {};
 template <class CP> struct FoldsDensity<CP, std::void_t<decltype(CP::FOLD)>> : std::integral_constant<bool, CP::FOLD> {};
 
 // a.xt: Morton-sorted targets; a.v_trg / a.partial: indexed like a.xt (the caller scatters back).
+// A folding policy (fp64 single layer): a.xn = the block fold_prepass_kernel wrote for THIS launch's densities and splits (gridDim.y, a.chunk).
 // (asking the compiler for 5-6 waves/SIMD instead of the 4 its registers allow, or unrolling the far loop by 2 or 8 instead of 4, costs 0-3 %:
 // profiles/r03_ab_centered_occupancy.txt)
 template <class CP, class R, int MODE, int T, int UNR = 4>
@@ -378,14 +374,17 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
   using Ker = typename CP::Ker;
   constexpr int ND = Ker::ND, K0 = Ker::K0, K1 = Ker::K1, NF = CP::NF;
   constexpr bool SCALAR = (K1 == 1 && NF == 1);               // far and near pairs add into ONE sum per target (the Laplace single and double layer)
-  constexpr int kNearCap = CP::NEAR_CAP < sctl_amd::kNearCap ? CP::NEAR_CAP : sctl_amd::kNearCap;
+  // (FOLD stages two tiles per step and makes room for both beforehand: 144 records, with which 16 waves' LDS still fit a CU)
+  constexpr int kNearCap = FoldsDensity<CP>::value ? 144 : (CP::NEAR_CAP < sctl_amd::kNearCap ? CP::NEAR_CAP : sctl_amd::kNearCap);
   constexpr int NEARW = (Ker::NREC + 3) / 4;                  // Rec4 groups of a near record (the kernel's packed exact record)
   constexpr int XV = (CP::XW * (int)sizeof(R) + 15) / 16;     // 16-byte words of the extra far record
   constexpr bool FOLD = FoldsDensity<CP>::value;
-  // far records: one list, or (FOLD) the positive list from the front and the negative one from the back, each with its own leftovers (< UNR)
-  constexpr int FAR_CAP = FOLD ? kWaveTile + 2 * (UNR - 1) : kWaveTile + UNR;
+  // far records: one list, or (FOLD) the positive list from the front and the negative one from the back, a tile and its own leftovers (< UNR) each
+  constexpr int FAR_CAP = FOLD ? 2 * (kWaveTile + UNR - 1) : kWaveTile + UNR;
   __shared__ V farB[FAR_CAP * NW];                            // {x', y', z', |x_s'|^2}   (+ the leftovers of earlier tiles)
-  __shared__ V farXv[FAR_CAP * (XV > 0 ? XV : 1)];              // the policy's extra far reals (density, or the normal terms)
+  // the policy's extra far reals (density, or the normal terms); FOLD, whose lists hold two tiles: the one real k per record packed (16 waves' LDS per CU)
+  constexpr int FARX_WORDS = FOLD ? (FAR_CAP * CP::XW * (int)sizeof(R) + 15) / 16 : FAR_CAP * (XV > 0 ? XV : 1);
+  __shared__ V farXv[FARX_WORDS];
   __shared__ V nearA[(kNearCap + 2) * NW * NEARW];            // packed exact records; near sources are collected over
                                                               // several tiles and evaluated in batches, so the exact loop runs
                                                               // rarely and with a long trip count
@@ -463,7 +462,9 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
       for (int k = 0; k < K0; k++) f[k] = a.f[s * K0 + k];
     }
   };
-  if (ntile > 0) load_source(0);
+  if constexpr (!FOLD) {   // (a folding policy reads the records of the launch's pre-pass)
+    if (ntile > 0) load_source(0);
+  }
 
   // ---- near sources: the reference-exact pair (d = x_t - x_s, masked at r = 0), evaluated in batches -----------
   const R far_off = R(1.0e3) * (R(1) + sqrt_(rt2));
@@ -579,34 +580,53 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
   // of being padded with null sources (1.5 evaluations in ~62 per tile): +0.9 % (A/B, profiles/r02_ab_far_carry.txt).  fp32, whose tile
   // costs a third of the cycles, gains nothing from it and pads every tile.  A policy that folds the density into its far records (FOLD) keeps
   // two such lists, one per sign, each with its own leftovers; no folded record contributes exactly 0, so the last leftovers are not padded.
+  // (Until round 16 every wave sorted each tile's sources by sign and classified their densities itself, the division k = 1 / f^2 included:
+  // 75 vector instructions per tile outside the loops.  Both depend on the density alone and are now decided once per launch.)
   if constexpr (FOLD) {
-    static_assert(SCALAR && NF == 1, "the fold is the single layer's");
-    // stage_tile with the far sources split by the sign of the density into the positive list (records [0, n+) of farB / farX, leftovers
-    // of earlier tiles first) and the negative list (records FAR_CAP - 1 - i, i in [0, n-)).  Sets the numbers of new far sources of either sign.
-    // The two lists never meet: n+ + n- <= 64 + 2 (UNR - 1) = FAR_CAP.
-    auto stage_tile_folded = [&](int it, int cpos, int cneg, int& npos, int& nneg) {
-      const int ns = (it == ntile - 1) ? (int)(len - (int64_t)it * kWaveTile) : kWaveTile;
-      const bool valid = lane < ns;
+    static_assert(SCALAR && NF == 1 && std::is_same<R, double>::value, "the fold is the fp64 single layer's");
+    // The sources come from the launch's pre-pass (fold_prepass_kernel below; fold_prepass.hpp has the layout), not from a.xs / a.f: per split, tiles of 64
+    // records {x, y, z, k = 1 / f^2} that hold ONE sign — positive tiles from the front of the split's area, negative ones from its back —, the last tile of
+    // either sign padded with records of k = 0, and a list of the sources that cannot be folded for any centre.  a.xn carries the block: a folding policy has
+    // no normals.  What is left per (wave, tile) is what depends on the centre: p = x - c, the far test and the band test on k |x_s'|^2 and |x_s'|^2.
+    static_assert(ND == 0 && K0 == 1, "a.xn is free to carry the pre-pass block");
+    const FoldPrepLayout L((int64_t)gridDim.y, a.chunk);
+    const char* const blk = (const char*)a.xn;
+    const int32_t* const hdr = (const int32_t*)blk + 4 * (int64_t)split_idx;
+    const int npt = hdr[0], nnt = hdr[1], nexc = hdr[2];   // tiles of either sign, exceptions (wave-uniform)
+    const int cap = (int)L.cap;
+    const V* const rec = (const V*)(blk + L.rec) + (int64_t)split_idx * cap * NW;
+    const uint32_t* const ridx = (const uint32_t*)(blk + L.idx) + (int64_t)split_idx * cap;
+    const uint32_t* const exc = (const uint32_t*)(blk + L.exc) + (int64_t)split_idx * a.chunk;
+    R kf = 0;   // k of the lane's record; x[] its coordinates
+    auto load_rec = [&](int r0) {
+      const R* const w = (const R*)(rec + (int64_t)r0 * NW) + lane * 4;   // (r0 is wave-uniform)
+      x[0] = w[0]; x[1] = w[1]; x[2] = w[2]; kf = w[3];
+    };
+    // One tile of one sign (records r0 + lane): the positive list is records [0, n+) of farB / farX, leftovers of earlier tiles first, the negative
+    // list records FAR_CAP - 1 - i, i in [0, n-).  Returns the number of new far records.  The two lists never meet: n+ + n- <= 2 (64 + UNR - 1) = FAR_CAP.
+    auto stage_rec = [&](int r0, int carry, auto neg) -> int {
+      constexpr bool NEG = decltype(neg)::value;
       const R p[3] = {x[0] - c[0], x[1] - c[1], x[2] - c[2]};
-      const R ss = len2(p);
-      const bool far = valid && (ss > near_r2);
-      R k = 0;
-      const int cls = far ? CP::fold_class(f[0], ss, k) : 2;
-      const bool is_pos = far && cls == 1, is_neg = far && cls == -1, is_near = valid && cls == 2;
-      const unsigned long long bp = __ballot(is_pos), bq = __ballot(is_neg), bn = __ballot(is_near);
-      const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-      const int nnear = __popcll(bn);
-      __syncthreads();   // previous tile's far records fully consumed
-      if (nn + nnear > kNearCap) {   // wave-uniform: evaluate the pending near sources before the list overflows
-        flush_near();
-        __syncthreads();
+      const R ss = len2(p), kss = kf * ss;
+      const bool valid = kf != R(0);   // (padding; the valid records of a tile come first)
+      // the bands of the fold: the terms of r2' are at most ~2.5 k |x_s'|^2 (a far source has r^2 >= |x_s'|^2 / 4), and |k x_s'| = k |x_s'|^2 / |x_s'| <= 2^750
+      const bool far = valid && ss > near_r2 && kss >= R(0x1p-600) && kss <= R(0x1p600) && ss >= R(0x1p-300) && ss <= R(0x1p300);
+      const unsigned long long bv = __ballot(valid), bf = __ballot(far);
+      if (bf == bv) {   // wave-uniform, the common case (~0.5 near sources are expected per tile): no prefix counts
+        if (valid) CP::put_folded(farB, farX, NEG ? FAR_CAP - 1 - (carry + lane) : carry + lane, p, ss, kf);
+        return __popcll(bv);
       }
-      if (is_pos) CP::put_folded(farB, farX, cpos + __popcll(bp & below), p, ss, k);
-      else if (is_neg) CP::put_folded(farB, farX, FAR_CAP - 1 - (cneg + __popcll(bq & below)), p, ss, k);
-      else if (is_near) put_near(nn + __popcll(bn & below), x, nrm, f);
+      const unsigned long long bn = bv & ~bf, below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+      const int nnear = __popcll(bn);
+      if (far) {
+        const int q = carry + __popcll(bf & below);
+        CP::put_folded(farB, farX, NEG ? FAR_CAP - 1 - q : q, p, ss, kf);
+      } else if (valid) {   // the exact pair wants the density itself
+        const R fq[K0] = {a.f[s_begin + ridx[r0 + lane]]};
+        put_near(nn + __popcll(bn & below), x, nrm, fq);
+      }
       nn += nnear;
-      npos = __popcll(bp);
-      nneg = __popcll(bq);
+      return __popcll(bf);
     };
     // one far record into tacc; NEG: record i of the negative list, subtracted
     auto far_folded = [&](R (&tacc)[T][NF], int i, auto neg) {
@@ -645,18 +665,38 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
 #pragma unroll
       for (int j = 0; j < T; j++) acc[j][0] += tacc[j][0];
     };
-    int cpos = 0, cneg = 0;   // leftovers of either list from the previous tiles (wave-uniform, < UNR each)
-    for (int it = 0; it < ntile; it++) {
-      int npos, nneg;
-      stage_tile_folded(it, cpos, cneg, npos, nneg);
+    // A step takes the it-th tile of either sign — while both signs last, a positive and a negative tile, 128 sources — in the order P0 N0 P1 N1 ...; the
+    // records of the tile after the one being staged are loaded meanwhile (one tile's worth of registers: the load of a step's second tile is not hidden
+    // behind a far loop, only behind the other waves of the SIMD)
+    const std::integral_constant<bool, false> pos;
+    const std::integral_constant<bool, true> neg;
+    const int nstep = npt > nnt ? npt : nnt;
+    int cpos = 0, cneg = 0;   // leftovers of either list from the previous steps (wave-uniform, < UNR each)
+    if (nstep > 0) load_rec((int)fold_prep_tile_base(npt == 0, 0, cap));
+    for (int it = 0; it < nstep; it++) {
+      const bool hp = it < npt, hn = it < nnt;
+      int npos = 0, nneg = 0;
+      __syncthreads();   // previous step's far records fully consumed
+      if (hp) {
+        npos = stage_rec(it * kWaveTile, cpos, pos);
+        if (hn) load_rec((int)fold_prep_tile_base(true, it, cap));
+      }
+      if (hn) nneg = stage_rec((int)fold_prep_tile_base(true, it, cap), cneg, neg);
+      // The pending near sources are evaluated HERE when the next step's two tiles might not fit behind them, not inside a tile's staging: between the
+      // staging and the next loads no record is in registers, and the exact loop is the kernel's register peak (134 against 126 registers otherwise)
+      if (nn > kNearCap - 2 * kWaveTile) {   // wave-uniform
+        __syncthreads();
+        flush_near();
+      }
+      if (it + 1 < npt) load_rec((it + 1) * kWaveTile);
+      else if (it + 1 < nnt) load_rec((int)fold_prep_tile_base(true, it + 1, cap));
       const int np = cpos + npos, nq = cneg + nneg, mp = np & ~(UNR - 1), mq = nq & ~(UNR - 1);
-      if (it + 1 < ntile) load_source(it + 1);
       __syncthreads();
       run_far_folded(mp, mq);
       cpos = np - mp;
       cneg = nq - mq;
       // the leftovers to the front of their list (one wave: its LDS operations complete in program order; the lists do not overlap): lanes [0, cpos)
-      // move the positive ones, lanes [32, 32 + cneg) the negative ones
+      // move the positive ones, lanes [32, 32 + cneg) the negative ones.  Full tiles that are all far leave nothing to move.
       const bool mv_pos = mp > 0 && lane < cpos, mv_neg = mq > 0 && lane >= 32 && lane < 32 + cneg;
       if (mv_pos || mv_neg) {
         const int from = mv_pos ? mp + lane : FAR_CAP - 1 - (mq + lane - 32), to = mv_pos ? lane : FAR_CAP - 1 - (lane - 32);
@@ -674,10 +714,25 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
       R tacc[T][NF];
 #pragma unroll
       for (int j = 0; j < T; j++) tacc[j][0] = 0;
-      for (int i = 0; i < cpos; i++) far_folded(tacc, i, std::integral_constant<bool, false>());
-      for (int i = 0; i < cneg; i++) far_folded(tacc, i, std::integral_constant<bool, true>());
+      for (int i = 0; i < cpos; i++) far_folded(tacc, i, pos);
+      for (int i = 0; i < cneg; i++) far_folded(tacc, i, neg);
 #pragma unroll
       for (int j = 0; j < T; j++) acc[j][0] += tacc[j][0];
+    }
+    // the sources that no centre can fold (density not finite, or k out of every band): the exact pair, as the near sources
+    for (int e0 = 0; e0 < nexc; e0 += kWaveTile) {
+      const int ne = (nexc - e0 < kWaveTile) ? nexc - e0 : kWaveTile;
+      if (nn + ne > kNearCap) {
+        __syncthreads();
+        flush_near();
+        __syncthreads();
+      }
+      if (lane < ne) {
+        const int64_t s = s_begin + exc[e0 + lane];
+        const R xq[3] = {a.xs[s * 3], a.xs[s * 3 + 1], a.xs[s * 3 + 2]}, fq[K0] = {a.f[s]};
+        put_near(nn + lane, xq, nrm, fq);
+      }
+      nn += ne;
     }
   } else if constexpr (sizeof(R) == 8) {
     int carry = 0;   // far records left over from the previous tiles (wave-uniform, < UNR)
@@ -733,6 +788,67 @@ __global__ void __launch_bounds__(kWaveBlock) centered_kernel(const EvalArgs<R> 
         }
       }
     }
+  }
+}
+
+// ---- the source pre-pass of the folding policy (fold_prepass.hpp: classes, slots, layout of the block) ---------
+// One workgroup per split walks its sources in order, kFoldPrepBlock at a time: ballots and per-wave counts give every source its rank within its
+// class — a fixed-order scan, no atomics, so the grouping and with it the kernel's sums are the same on every run.  Two count buffers, used in
+// turn, make one barrier per step enough.  ~20 us for 2^20 sources in 32 splits; the density changes from call to call, so it runs on every launch.
+constexpr int kFoldPrepBlock = 1024;
+__global__ void __launch_bounds__(kFoldPrepBlock) fold_prepass_kernel(const double* xs, const double* f, int64_t Ns, int64_t chunk, char* blk) {
+  constexpr int NWAVE = kFoldPrepBlock / 64;
+  __shared__ int cnt[2][3][NWAVE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t split = blockIdx.x;
+  const FoldPrepLayout L((int64_t)gridDim.x, chunk);
+  double* const rec = (double*)(blk + L.rec) + split * L.cap * 4;
+  uint32_t* const idx = (uint32_t*)(blk + L.idx) + split * L.cap;
+  uint32_t* const exc = (uint32_t*)(blk + L.exc) + split * chunk;
+  const int64_t s_begin = split * chunk;
+  const int64_t s_end = (s_begin + chunk < Ns) ? s_begin + chunk : Ns;
+  const int len = (int)((s_end > s_begin) ? s_end - s_begin : 0);
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  int npos = 0, nneg = 0, nexc = 0;   // sources of either class so far (uniform)
+  for (int off = 0, step = 0; off < len; off += kFoldPrepBlock, step++) {
+    const int o = off + tid;
+    double k;
+    const int cls = fold_prep_class(o < len ? f[s_begin + o] : 0.0, k);
+    const unsigned long long bp = __ballot(cls == 1), bq = __ballot(cls == -1), be = __ballot(cls == 2);
+    int (*const cn)[NWAVE] = cnt[step & 1];
+    if (lane == 0) { cn[0][wave] = __popcll(bp); cn[1][wave] = __popcll(bq); cn[2][wave] = __popcll(be); }
+    __syncthreads();
+    int before_p = 0, before_q = 0, before_e = 0, tot_p = 0, tot_q = 0, tot_e = 0;
+#pragma unroll
+    for (int w = 0; w < NWAVE; w++) {
+      const int vp = cn[0][w], vq = cn[1][w], ve = cn[2][w];
+      tot_p += vp; tot_q += vq; tot_e += ve;
+      if (w < wave) { before_p += vp; before_q += vq; before_e += ve; }
+    }
+    if (cls == 1 || cls == -1) {
+      const bool neg = cls == -1;
+      const int rank = neg ? nneg + before_q + __popcll(bq & below) : npos + before_p + __popcll(bp & below);
+      const int64_t slot = fold_prep_slot(neg, rank, L.cap), s = s_begin + o;
+      rec[slot * 4] = xs[s * 3]; rec[slot * 4 + 1] = xs[s * 3 + 1]; rec[slot * 4 + 2] = xs[s * 3 + 2]; rec[slot * 4 + 3] = k;
+      idx[slot] = (uint32_t)o;
+    } else if (cls == 2) {
+      exc[nexc + before_e + __popcll(be & below)] = (uint32_t)o;
+    }
+    npos += tot_p; nneg += tot_q; nexc += tot_e;
+  }
+  // the last tile of either sign filled up with records of k = 0; the split's header
+#pragma unroll
+  for (int sgn = 0; sgn < 2; sgn++) {
+    const int n = sgn ? nneg : npos, fill = (int)fold_prep_tiles(n) * kFoldTile - n;
+    if (tid < fill) {
+      const int64_t slot = fold_prep_slot(sgn == 1, n + tid, L.cap);
+      rec[slot * 4] = 0; rec[slot * 4 + 1] = 0; rec[slot * 4 + 2] = 0; rec[slot * 4 + 3] = 0;
+      idx[slot] = 0;
+    }
+  }
+  if (tid == 0) {
+    int32_t* const hdr = (int32_t*)blk + 4 * split;
+    hdr[0] = (int32_t)fold_prep_tiles(npos); hdr[1] = (int32_t)fold_prep_tiles(nneg); hdr[2] = nexc; hdr[3] = 0;
   }
 }
 
