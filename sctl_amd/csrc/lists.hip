@@ -2,8 +2,7 @@
 // A plan validates the lists, groups them by target range (a leaf box and ALL the source boxes listed for it become the work of
 // whole waves), orders the work items by cost and keeps them on the device; an evaluation is ONE launch.
 #include "internal.hpp"
-#include "lists_multi_kernel.hpp"
-#include "lists_multi_transpose_kernel.hpp"
+#include "lists_rows_kernel.hpp"
 #include "workspace.hpp"
 
 #include <algorithm>
@@ -167,6 +166,57 @@ int plan_side(int64_t nlists, const int64_t* own_off, const int64_t* own_cnt, co
   out.longest = longest;
   return SCTL_AMD_OK;
 }
+
+// A host-pointer evaluation of nd rows in either direction, after the entry's own checks: device copies of the caller's arrays and pinned staging, kept on
+// the handle and grown on demand.  Slots [0] r_trg, [1] r_src, [2] n_src, [3] nd rows of Ns x K0, [4] nd rows of Nt x K1.  FORWARD sends `in` (v_src) in [3]
+// and returns [4] (v_trg); TRANSPOSE sends `in` (w_trg) in [4] and returns [3] (g_src).  Coordinates and normals go down once, the nd input rows in one
+// transfer; the output slot is zeroed, filled by the direction's _device entry (nd == 1: the single-row kernel), comes back in one transfer and is added
+// into `out` (the accumulate semantics of GenericKernel::Eval).
+int lists_host_call(sctl_amd_lists* p, bool transpose, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* in, void* out, int digits,
+                    const void* ctx, int ctx_bytes) {
+  const KernelEntry& k = *p->k;
+  const size_t rs = real_size(p->real);
+  const int slot_out = transpose ? 3 : 4;
+  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
+  const void* src[5] = {r_trg, r_src, n_src, transpose ? nullptr : in, transpose ? in : nullptr};
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  size_t total = 0;
+  for (int i = 0; i < 5; i++) {
+    total += Carver::pad(bytes[i]);
+    if (bytes[i] > p->dcap[i]) {
+      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
+      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
+      p->dcap[i] = bytes[i];
+    }
+  }
+  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
+    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
+    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
+    p->pinned_cap = total;
+  }
+  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
+  const bool same = r_src == r_trg && bytes[0] == bytes[1];
+  Carver cut(p->pinned);
+  char* back = nullptr;
+  for (int i = 0; i < 5; i++) {
+    char* q = cut.take<char>(bytes[i]);
+    if (i == slot_out) { back = q; continue; }
+    if (!bytes[i] || (i == 1 && same)) continue;
+    std::memcpy(q, src[i], bytes[i]);
+    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
+  }
+  LISTS_TRY(hipMemsetAsync(p->dbuf[slot_out], 0, bytes[slot_out], p->st));
+  void* const d_src = same ? p->dbuf[0] : p->dbuf[1];
+  const int rc = transpose ? sctl_amd_lists_eval_transpose_densities_device(p, nd, p->dbuf[0], d_src, p->dbuf[2], p->dbuf[4], p->dbuf[3], digits, ctx, ctx_bytes, p->st)
+                           : sctl_amd_lists_eval_densities_device(p, nd, p->dbuf[0], d_src, p->dbuf[2], p->dbuf[3], p->dbuf[4], digits, ctx, ctx_bytes, p->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[slot_out], bytes[slot_out], hipMemcpyDeviceToHost, p->st));
+  LISTS_TRY(hipStreamSynchronize(p->st));
+  add_into(p->real, out, back, (int64_t)nd * (transpose ? p->Ns * k.k0 : p->Nt * k.k1));
+  return SCTL_AMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -317,43 +367,7 @@ int sctl_amd_lists_eval_host(sctl_amd_lists* p, const void* r_trg, const void* r
   if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (p->side[0].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
-  const size_t rs = real_size(p->real);
-  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
-  const void* src[4] = {r_trg, r_src, n_src, v_src};
-  DeviceScope scope(p->device);
-  LISTS_TRY(scope.err);
-  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-  size_t total = 0;
-  for (int i = 0; i < 5; i++) {
-    total += Carver::pad(bytes[i]);
-    if (bytes[i] > p->dcap[i]) {
-      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
-      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
-      p->dcap[i] = bytes[i];
-    }
-  }
-  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
-    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
-    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
-    p->pinned_cap = total;
-  }
-  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
-  const bool same = r_src == r_trg && bytes[0] == bytes[1];
-  Carver cut(p->pinned);
-  for (int i = 0; i < 4; i++) {
-    char* q = cut.take<char>(bytes[i]);
-    if (!bytes[i] || (i == 1 && same)) continue;
-    std::memcpy(q, src[i], bytes[i]);
-    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
-  }
-  LISTS_TRY(hipMemsetAsync(p->dbuf[4], 0, bytes[4], p->st));
-  const int rc = sctl_amd_lists_eval_device(p, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[3], p->dbuf[4], digits, ctx, ctx_bytes, p->st);
-  if (rc != SCTL_AMD_OK) return rc;
-  char* back = cut.take<char>(bytes[4]);
-  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[4], bytes[4], hipMemcpyDeviceToHost, p->st));
-  LISTS_TRY(hipStreamSynchronize(p->st));
-  add_into(p->real, v_trg, back, p->Nt * k.k1);      // v_trg += device result (accumulate semantics of GenericKernel::Eval)
-  return SCTL_AMD_OK;
+  return lists_host_call(p, false, 1, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
 }
 
 // ---- the transposed sum over the lists (sctl_amd_lists_eval_transpose_*, lists_transpose_kernel.hpp) -----------------------------------
@@ -395,45 +409,7 @@ int sctl_amd_lists_eval_transpose_host(sctl_amd_lists* p, const void* r_trg, con
   if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   if (p->side[1].nitems == 0) return SCTL_AMD_OK;
   if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
-  const size_t rs = real_size(p->real);
-  // the forward entry's buffers with the roles of the last two exchanged: [3] (the size of v_src) receives g_src, [4] (the size of v_trg) holds w_trg
-  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs};
-  const void* src[5] = {r_trg, r_src, n_src, nullptr, w_trg};
-  DeviceScope scope(p->device);
-  LISTS_TRY(scope.err);
-  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-  size_t total = 0;
-  for (int i = 0; i < 5; i++) {
-    total += Carver::pad(bytes[i]);
-    if (bytes[i] > p->dcap[i]) {
-      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
-      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
-      p->dcap[i] = bytes[i];
-    }
-  }
-  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
-    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
-    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
-    p->pinned_cap = total;
-  }
-  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
-  const bool same = r_src == r_trg && bytes[0] == bytes[1];
-  Carver cut(p->pinned);
-  char* back = nullptr;
-  for (int i = 0; i < 5; i++) {
-    char* q = cut.take<char>(bytes[i]);
-    if (i == 3) { back = q; continue; }
-    if (!bytes[i] || (i == 1 && same)) continue;
-    std::memcpy(q, src[i], bytes[i]);
-    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
-  }
-  LISTS_TRY(hipMemsetAsync(p->dbuf[3], 0, bytes[3], p->st));
-  const int rc = sctl_amd_lists_eval_transpose_device(p, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[4], p->dbuf[3], digits, ctx, ctx_bytes, p->st);
-  if (rc != SCTL_AMD_OK) return rc;
-  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[3], bytes[3], hipMemcpyDeviceToHost, p->st));
-  LISTS_TRY(hipStreamSynchronize(p->st));
-  add_into(p->real, g_src, back, p->Ns * k.k0);      // g_src += device result
-  return SCTL_AMD_OK;
+  return lists_host_call(p, true, 1, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes);
 }
 
 // one-shot form: plan the transposed side only, evaluate, release
@@ -448,36 +424,45 @@ int sctl_amd_eval_lists_transpose_host(int kernel, int real, int64_t nlists, con
   return rc;
 }
 
-// ---- several densities over the lists (sctl_amd_lists_eval_densities_*, lists_multi_kernel.hpp) ----------------------------------------
-// The plan is the single-density plan: the same handle serves any nd.
+// ---- several rows over the lists, either direction (lists_rows_kernel.hpp): several densities (sctl_amd_lists_eval_densities_*) ... -----------------
+// The plan is the single-row plan: the same handle serves any nd.
 }  // extern "C"
 
 namespace sctl_amd {
 namespace {
-// Launch table of the several-densities list forms: the built-in kernels only; a registered plugin kernel has none (null) and is evaluated one
-// density at a time.
-const ListsMultiEntry* lmulti_entry(int kernel_id) {
-  static const ListsMultiEntry* tab[SCTL_AMD_NUM_KERNELS] = {
-      &lmulti_Laplace3D_FxU(), &lmulti_Laplace3D_DxU(), &lmulti_Laplace3D_FxdU(),  &lmulti_Stokes3D_FxU(),      &lmulti_Stokes3D_DxU(),
-      &lmulti_Stokes3D_FxT(),  &lmulti_Stokes3D_FSxU(), &lmulti_Stokes3D_FxUP(), &lmulti_Laplace3D_FDxUdU(), &lmulti_Helmholtz3D_FxU()};
-  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+// Launch table of the several-rows list forms of a direction (Dir: ListFwd, ListTrans): the built-in kernels only; a registered plugin kernel has none
+// (null) and runs its rows one at a time.
+template <class Dir> const ListsRowsEntry<Dir>* multi_entry(int kernel_id) {
+  if (kernel_id < 0 || kernel_id >= SCTL_AMD_NUM_KERNELS) return nullptr;
+  if constexpr (Dir::SIDE == 0) {
+    static const ListsMultiEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+        &lmulti_Laplace3D_FxU(), &lmulti_Laplace3D_DxU(), &lmulti_Laplace3D_FxdU(),  &lmulti_Stokes3D_FxU(),      &lmulti_Stokes3D_DxU(),
+        &lmulti_Stokes3D_FxT(),  &lmulti_Stokes3D_FSxU(), &lmulti_Stokes3D_FxUP(), &lmulti_Laplace3D_FDxUdU(), &lmulti_Helmholtz3D_FxU()};
+    return tab[kernel_id];
+  } else {
+    static const ListsMultiTEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+        &ltmulti_Laplace3D_FxU(), &ltmulti_Laplace3D_DxU(), &ltmulti_Laplace3D_FxdU(),  &ltmulti_Stokes3D_FxU(),      &ltmulti_Stokes3D_DxU(),
+        &ltmulti_Stokes3D_FxT(),  &ltmulti_Stokes3D_FSxU(), &ltmulti_Stokes3D_FxUP(), &ltmulti_Laplace3D_FDxUdU(), &ltmulti_Helmholtz3D_FxU()};
+    return tab[kernel_id];
+  }
 }
-template <class R> ListsMultiLaunch<R> lmulti_launch(const ListsMultiEntry& me, int mode, int form) {
+template <class Dir, class R> ListsRowsLaunch<Dir, R> multi_launch(const ListsRowsEntry<Dir>& me, int mode, int form) {
   if constexpr (std::is_same<R, double>::value) return me.f64[mode][form];
   else return me.f32[mode][form];
 }
-// the form for `left` >= 2 densities still to do: the narrowest that takes them all, else the widest; -1: none (the single-density kernel)
-template <class R> int lmulti_form(const ListsMultiEntry* me, int mode, int left) {
+// the form for `left` >= 2 rows still to do: the narrowest that takes them all, else the widest; -1: none (the single-row kernel)
+template <class Dir, class R> int multi_form(const ListsRowsEntry<Dir>* me, int mode, int left) {
   if (!me || left < 2) return -1;
   int widest = -1;
-  for (int i = 0; i < kNumListMultiM; i++) {
-    if (!lmulti_launch<R>(*me, mode, i)) continue;
-    if (kListMultiM[i] >= left) return i;
+  for (int i = 0; i < kNumListRowsM; i++) {
+    if (!multi_launch<Dir, R>(*me, mode, i)) continue;
+    if (kListRowsM[i] >= left) return i;
     widest = i;
   }
   return widest;
 }
 
+// (the two entries check in different orders: the context comes last forward, right after the handle transposed)
 int check_lists_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
   if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
   if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
@@ -486,35 +471,49 @@ int check_lists_densities(const sctl_amd_lists* p, int nd, const void* ctx, int 
   if (const int rc = check_ctx(k, ctx, ctx_bytes)) return rc;
   return SCTL_AMD_OK;
 }
+int check_lists_transpose_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  if (const int rc = check_ctx(*p->k, ctx, ctx_bytes)) return rc;
+  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
+  if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
+  return SCTL_AMD_OK;
+}
 
-// nd >= 2 densities, density-major, on the plan's device: passes of the widest form, then the narrowest form that holds the rest; one density
-// left over (and every density of a plugin kernel) takes the single-density kernel on the same stream.  v is accumulated into.
-template <class R>
-int lists_eval_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits, const void* ctx, int ctx_bytes,
-                           hipStream_t st) {
+// nd >= 2 rows, row-major, on the plan's device: passes of the widest form, then the narrowest form that holds the rest; one row left over (and every
+// row of a plugin kernel) takes the single-row kernel of the direction on the same stream.  FORWARD: in = v_src (rows of Ns x K0), out = v_trg (rows of
+// Nt x K1); TRANSPOSE: in = w_trg (rows of Nt x K1), out = g_src (rows of Ns x K0).  out is accumulated into.
+template <class Dir, class R>
+int lists_eval_rows(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* in, R* out, int digits, const void* ctx, int ctx_bytes, hipStream_t st) {
+  constexpr bool transpose = Dir::SIDE == 1;
   const KernelEntry& k = *p->k;
-  const ListsSide& fw = p->side[0];
-  const int64_t f_stride = p->Ns * k.k0, v_stride = p->Nt * k.k1;
-  const ListsMultiEntry* me = lmulti_entry(k.id);
+  const ListsSide& sd = p->side[Dir::SIDE];
+  const int64_t in_stride = transpose ? p->Nt * k.k1 : p->Ns * k.k0, out_stride = transpose ? p->Ns * k.k0 : p->Nt * k.k1;
+  const ListsRowsEntry<Dir>* me = multi_entry<Dir>(k.id);
   const int mode = mode_for(p->real, digits);
   for (int m0 = 0; m0 < nd;) {
-    const int form = lmulti_form<R>(me, mode, nd - m0);
+    const R* const in0 = in + m0 * in_stride;
+    R* const out0 = out + m0 * out_stride;
+    const int form = multi_form<Dir, R>(me, mode, nd - m0);
     if (form < 0) {
-      const int rc = sctl_amd_lists_eval_device(p, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride, digits, ctx, ctx_bytes, st);
+      const int rc = transpose ? sctl_amd_lists_eval_transpose_device(p, xt, xs, xn, in0, out0, digits, ctx, ctx_bytes, st)
+                               : sctl_amd_lists_eval_device(p, xt, xs, xn, in0, out0, digits, ctx, ctx_bytes, st);
       if (rc) return rc;
       m0++;
       continue;
     }
-    const int M = kListMultiM[form], nact = nd - m0 < M ? nd - m0 : M;
+    const int M = kListRowsM[form], nact = nd - m0 < M ? nd - m0 : M;
     (void)hipGetLastError();
-    ListMultiArgs<R> a{};
-    a.l = ListArgs<R>{{0}, (const ListItem*)fw.d_items, (const ListRange*)fw.d_ranges, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride,
-                      (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)fw.d_groups, (const uint32_t*)fw.d_flat};
-    std::memcpy(a.l.xcd_first, fw.xcd_first, sizeof a.l.xcd_first);
-    a.f_stride = f_stride; a.v_stride = v_stride; a.nact = nact;
-    lmulti_launch<R>(*me, mode, form)(a, fw.nblocks, st);
+    const R scale = (R)(k.scale / k.acc_factor[mode]);
+    typename Dir::template Args<R> a{};
+    if constexpr (transpose)
+      a.l = ListTArgs<R>{{0}, (const ListItem*)sd.d_items, (const ListRange*)sd.d_ranges, xs, xn, xt, in0, out0, scale, make_ctx(k, ctx), (const PackedGroup*)sd.d_groups, (const uint32_t*)sd.d_flat};
+    else
+      a.l = ListArgs<R>{{0}, (const ListItem*)sd.d_items, (const ListRange*)sd.d_ranges, xt, xs, xn, in0, out0, scale, make_ctx(k, ctx), (const PackedGroup*)sd.d_groups, (const uint32_t*)sd.d_flat};
+    std::memcpy(a.l.xcd_first, sd.xcd_first, sizeof a.l.xcd_first);
+    a.in_stride = in_stride; a.out_stride = out_stride; a.nact = nact;
+    multi_launch<Dir, R>(*me, mode, form)(a, sd.nblocks, st);
     LISTS_TRY(hipGetLastError());
-    count_work(fw.pairs * nact, k);
+    count_work(sd.pairs * nact, k);
     m0 += nact;
   }
   return SCTL_AMD_OK;
@@ -533,11 +532,10 @@ int sctl_amd_lists_eval_densities_device(sctl_amd_lists* p, int nd, const void* 
   if (!r_trg || !r_src || !v_src || !v_trg || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device
   LISTS_TRY(scope.err);
-  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_densities_t<R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)v_src, (R*)v_trg, digits, ctx, ctx_bytes, (hipStream_t)stream); });
+  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_rows<ListFwd, R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)v_src, (R*)v_trg, digits, ctx, ctx_bytes, (hipStream_t)stream); });
 }
 
-// Coordinates and normals go down once, the nd density rows in one transfer, the nd result rows come back in one; the handle's device buffers
-// and pinned block are the single-density entry's, grown to nd rows on demand.
+// (the handle's device buffers and pinned block are the single-density entry's, grown to nd rows on demand: lists_host_call)
 int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, void* v_trg,
                                        int digits, const void* ctx, int ctx_bytes) {
   const int rc0 = check_lists_densities(p, nd, ctx, ctx_bytes);
@@ -546,44 +544,7 @@ int sctl_amd_lists_eval_densities_host(sctl_amd_lists* p, int nd, const void* r_
   if (nd == 0 || p->side[0].nitems == 0) return SCTL_AMD_OK;
   const KernelEntry& k = *p->k;
   if (!r_trg || !r_src || !v_src || !v_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or potential array");
-  const size_t rs = real_size(p->real);
-  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
-  const void* src[4] = {r_trg, r_src, n_src, v_src};
-  DeviceScope scope(p->device);
-  LISTS_TRY(scope.err);
-  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-  size_t total = 0;
-  for (int i = 0; i < 5; i++) {
-    total += Carver::pad(bytes[i]);
-    if (bytes[i] > p->dcap[i]) {
-      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
-      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
-      p->dcap[i] = bytes[i];
-    }
-  }
-  if (total > p->pinned_cap) {
-    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
-    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
-    p->pinned_cap = total;
-  }
-  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
-  const bool same = r_src == r_trg && bytes[0] == bytes[1];
-  Carver cut(p->pinned);
-  for (int i = 0; i < 4; i++) {
-    char* q = cut.take<char>(bytes[i]);
-    if (!bytes[i] || (i == 1 && same)) continue;
-    std::memcpy(q, src[i], bytes[i]);
-    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
-  }
-  LISTS_TRY(hipMemsetAsync(p->dbuf[4], 0, bytes[4], p->st));
-  const int rc = sctl_amd_lists_eval_densities_device(p, nd, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[3], p->dbuf[4], digits, ctx, ctx_bytes,
-                                                      p->st);
-  if (rc != SCTL_AMD_OK) return rc;
-  char* back = cut.take<char>(bytes[4]);
-  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[4], bytes[4], hipMemcpyDeviceToHost, p->st));
-  LISTS_TRY(hipStreamSynchronize(p->st));
-  add_into(p->real, v_trg, back, (int64_t)nd * p->Nt * k.k1);      // v_trg += device result, every row
-  return SCTL_AMD_OK;
+  return lists_host_call(p, false, nd, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
 }
 
 int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
@@ -598,81 +559,7 @@ int sctl_amd_eval_lists_densities_host(int kernel, int real, int nd, int64_t nli
   return rc;
 }
 
-// ---- several weight vectors through the transposed sum over the lists (sctl_amd_lists_eval_transpose_densities_*, lists_multi_transpose_kernel.hpp) ----
-// The plan is the single-vector transposed plan: the same handle serves any nd.
-}  // extern "C"
-
-namespace sctl_amd {
-namespace {
-// Launch table of the several-vectors transposed list forms: the built-in kernels only; a registered plugin kernel has none (null) and runs its
-// rows one at a time.
-const ListsMultiTEntry* ltmulti_entry(int kernel_id) {
-  static const ListsMultiTEntry* tab[SCTL_AMD_NUM_KERNELS] = {
-      &ltmulti_Laplace3D_FxU(), &ltmulti_Laplace3D_DxU(), &ltmulti_Laplace3D_FxdU(),  &ltmulti_Stokes3D_FxU(),      &ltmulti_Stokes3D_DxU(),
-      &ltmulti_Stokes3D_FxT(),  &ltmulti_Stokes3D_FSxU(), &ltmulti_Stokes3D_FxUP(), &ltmulti_Laplace3D_FDxUdU(), &ltmulti_Helmholtz3D_FxU()};
-  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
-}
-template <class R> ListsMultiTLaunch<R> ltmulti_launch(const ListsMultiTEntry& me, int mode, int form) {
-  if constexpr (std::is_same<R, double>::value) return me.f64[mode][form];
-  else return me.f32[mode][form];
-}
-// the form for `left` >= 2 rows still to do: the narrowest that takes them all, else the widest; -1: none (the single-vector kernel)
-template <class R> int ltmulti_form(const ListsMultiTEntry* me, int mode, int left) {
-  if (!me || left < 2) return -1;
-  int widest = -1;
-  for (int i = 0; i < kNumListMultiTM; i++) {
-    if (!ltmulti_launch<R>(*me, mode, i)) continue;
-    if (kListMultiTM[i] >= left) return i;
-    widest = i;
-  }
-  return widest;
-}
-
-int check_lists_transpose_densities(const sctl_amd_lists* p, int nd, const void* ctx, int ctx_bytes) {
-  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
-  if (const int rc = check_ctx(*p->k, ctx, ctx_bytes)) return rc;
-  if (nd < 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
-  if (!(p->directions & SCTL_AMD_LISTS_TRANSPOSE)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "this plan was not made for the TRANSPOSE direction");
-  return SCTL_AMD_OK;
-}
-
-// nd >= 2 weight vectors, row-major, on the plan's device: passes of the widest form, then the narrowest form that holds the rest; one row left
-// over (and every row of a plugin kernel) takes the single-vector transposed kernel on the same stream.  g is accumulated into.
-template <class R>
-int lists_eval_transpose_densities_t(sctl_amd_lists* p, int nd, const R* xt, const R* xs, const R* xn, const R* w, R* g, int digits, const void* ctx,
-                                     int ctx_bytes, hipStream_t st) {
-  const KernelEntry& k = *p->k;
-  const ListsSide& tr = p->side[1];
-  const int64_t w_stride = p->Nt * k.k1, g_stride = p->Ns * k.k0;
-  const ListsMultiTEntry* me = ltmulti_entry(k.id);
-  const int mode = mode_for(p->real, digits);
-  for (int m0 = 0; m0 < nd;) {
-    const int form = ltmulti_form<R>(me, mode, nd - m0);
-    if (form < 0) {
-      const int rc = sctl_amd_lists_eval_transpose_device(p, xt, xs, xn, w + m0 * w_stride, g + m0 * g_stride, digits, ctx, ctx_bytes, st);
-      if (rc) return rc;
-      m0++;
-      continue;
-    }
-    const int M = kListMultiTM[form], nact = nd - m0 < M ? nd - m0 : M;
-    (void)hipGetLastError();
-    ListMultiTArgs<R> a{};
-    a.l = ListTArgs<R>{{0}, (const ListItem*)tr.d_items, (const ListRange*)tr.d_ranges, xs, xn, xt, w + m0 * w_stride, g + m0 * g_stride,
-                       (R)(k.scale / k.acc_factor[mode]), make_ctx(k, ctx), (const PackedGroup*)tr.d_groups, (const uint32_t*)tr.d_flat};
-    std::memcpy(a.l.xcd_first, tr.xcd_first, sizeof a.l.xcd_first);
-    a.w_stride = w_stride; a.g_stride = g_stride; a.nact = nact;
-    ltmulti_launch<R>(*me, mode, form)(a, tr.nblocks, st);
-    LISTS_TRY(hipGetLastError());
-    count_work(tr.pairs * nact, k);
-    m0 += nact;
-  }
-  return SCTL_AMD_OK;
-}
-}  // namespace
-}  // namespace sctl_amd
-
-extern "C" {
-
+// ---- ... and several weight vectors through the transposed sum (sctl_amd_lists_eval_transpose_densities_*) ------------------------------------------
 int sctl_amd_lists_eval_transpose_densities_device(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg,
                                                    void* g_src, int digits, const void* ctx, int ctx_bytes, void* stream) {
   const int rc = check_lists_transpose_densities(p, nd, ctx, ctx_bytes);
@@ -682,11 +569,9 @@ int sctl_amd_lists_eval_transpose_densities_device(sctl_amd_lists* p, int nd, co
   if (!r_trg || !r_src || !w_trg || !g_src || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
   DeviceScope scope(p->device);      // the work list lives on the plan's device
   LISTS_TRY(scope.err);
-  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_transpose_densities_t<R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)w_trg, (R*)g_src, digits, ctx, ctx_bytes, (hipStream_t)stream); });
+  return with_real(p->real, [&](auto zero) { using R = decltype(zero); return lists_eval_rows<ListTrans, R>(p, nd, (const R*)r_trg, (const R*)r_src, (const R*)n_src, (const R*)w_trg, (R*)g_src, digits, ctx, ctx_bytes, (hipStream_t)stream); });
 }
 
-// Coordinates and normals go down once, the nd weight rows in one transfer, the nd result rows come back in one; the handle's device buffers
-// and pinned block are the single-vector entry's ([3] receives g_src, [4] holds w_trg), grown to nd rows on demand.
 int sctl_amd_lists_eval_transpose_densities_host(sctl_amd_lists* p, int nd, const void* r_trg, const void* r_src, const void* n_src, const void* w_trg,
                                                  void* g_src, int digits, const void* ctx, int ctx_bytes) {
   const int rc0 = check_lists_transpose_densities(p, nd, ctx, ctx_bytes);
@@ -695,45 +580,7 @@ int sctl_amd_lists_eval_transpose_densities_host(sctl_amd_lists* p, int nd, cons
   if (nd == 0 || p->side[1].nitems == 0) return SCTL_AMD_OK;
   const KernelEntry& k = *p->k;
   if (!r_trg || !r_src || !w_trg || !g_src || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, weight or result array");
-  const size_t rs = real_size(p->real);
-  const size_t bytes[5] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)nd * p->Ns * k.k0 * rs, (size_t)nd * p->Nt * k.k1 * rs};
-  const void* src[5] = {r_trg, r_src, n_src, nullptr, w_trg};
-  DeviceScope scope(p->device);
-  LISTS_TRY(scope.err);
-  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-  size_t total = 0;
-  for (int i = 0; i < 5; i++) {
-    total += Carver::pad(bytes[i]);
-    if (bytes[i] > p->dcap[i]) {
-      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
-      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
-      p->dcap[i] = bytes[i];
-    }
-  }
-  if (total > p->pinned_cap) {
-    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
-    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
-    p->pinned_cap = total;
-  }
-  // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
-  const bool same = r_src == r_trg && bytes[0] == bytes[1];
-  Carver cut(p->pinned);
-  char* back = nullptr;
-  for (int i = 0; i < 5; i++) {
-    char* q = cut.take<char>(bytes[i]);
-    if (i == 3) { back = q; continue; }
-    if (!bytes[i] || (i == 1 && same)) continue;
-    std::memcpy(q, src[i], bytes[i]);
-    LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
-  }
-  LISTS_TRY(hipMemsetAsync(p->dbuf[3], 0, bytes[3], p->st));
-  const int rc = sctl_amd_lists_eval_transpose_densities_device(p, nd, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[4], p->dbuf[3], digits, ctx,
-                                                                ctx_bytes, p->st);
-  if (rc != SCTL_AMD_OK) return rc;
-  LISTS_TRY(hipMemcpyAsync(back, p->dbuf[3], bytes[3], hipMemcpyDeviceToHost, p->st));
-  LISTS_TRY(hipStreamSynchronize(p->st));
-  add_into(p->real, g_src, back, (int64_t)nd * p->Ns * k.k0);      // g_src += device result, every row
-  return SCTL_AMD_OK;
+  return lists_host_call(p, true, nd, r_trg, r_src, n_src, w_trg, g_src, digits, ctx, ctx_bytes);
 }
 
 int sctl_amd_eval_lists_transpose_densities_host(int kernel, int real, int nd, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,

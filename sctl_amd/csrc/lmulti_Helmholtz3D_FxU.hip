@@ -1,8 +1,8 @@
-// Several-densities list forms of Helmholtz3D_FxU (lists_multi_kernel.hpp): widest form 4 densities in fp64, 8 in fp32.
-#include "lists_multi_kernel.hpp"
+// Several-densities list forms of Helmholtz3D_FxU (lists_multi_kernel, lists_rows_kernel.hpp): widest form 4 densities in fp64, 8 in fp32.
+#include "lists_rows_kernel.hpp"
 namespace sctl_amd {
 const ListsMultiEntry& lmulti_Helmholtz3D_FxU() {
-  static const ListsMultiEntry e = make_lists_multi_entry<Helmholtz3D_FxU, 4, 8>();
+  static const ListsMultiEntry e = make_lists_rows_entry<ListFwd, Helmholtz3D_FxU, 4, 8>();
   return e;
 }
 }  // namespace sctl_amd

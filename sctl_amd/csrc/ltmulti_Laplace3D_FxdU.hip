@@ -1,8 +1,8 @@
-// Transposed list forms of Laplace3D_FxdU for several weight vectors (lists_multi_transpose_kernel.hpp): widest form 8 weight vectors in fp64, 8 in fp32.
-#include "lists_multi_transpose_kernel.hpp"
+// Transposed list forms of Laplace3D_FxdU for several weight vectors (lists_multi_transpose_kernel, lists_rows_kernel.hpp): widest form 8 weight vectors in fp64, 8 in fp32.
+#include "lists_rows_kernel.hpp"
 namespace sctl_amd {
 const ListsMultiTEntry& ltmulti_Laplace3D_FxdU() {
-  static const ListsMultiTEntry e = make_lists_multi_t_entry<Laplace3D_FxdU, 8, 8>();
+  static const ListsMultiTEntry e = make_lists_rows_entry<ListTrans, Laplace3D_FxdU, 8, 8>();
   return e;
 }
 }  // namespace sctl_amd
