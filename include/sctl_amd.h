@@ -242,7 +242,7 @@ int sctl_amd_eval_transpose_plan(int kernel, int real, int64_t Nt, int64_t Ns, i
  * consecutive weight vectors, [nd][Nt*TrgDim], and g_src [nd][Ns*SrcDim]; row m is exactly what a single transposed call takes and
  * returns.  nd < 0 is SCTL_AMD_ERR_BAD_ARGUMENT, nd == 0 does nothing, and nd == 1 IS the single transposed entry (bit-identical results,
  * the same plan).  Argument errors return the codes of sctl_amd_eval_transpose_*, before any device work.  The built-in kernels run up to 8
- * weight vectors per pass (4 for the traction kernel) on the exact all-pairs kernel (csrc/multi_transpose_kernel.hpp): sums in a fixed
+ * weight vectors per pass (4 for the traction kernel) on the exact all-pairs kernel (csrc/rows_kernel.hpp): sums in a fixed
  * order, bit-reproducible; a registered kernel with pair_t (which has no several-vectors form) is evaluated one row at a time on the same
  * stream, one without pair_t is SCTL_AMD_ERR_UNKNOWN_KERNEL.  fp32 runs this exact pair at every `digits`, as the single transposed entry
  * does.  Counters grow by nd*Nt*Ns pairs.  Several weight vectors over the P2P lists:

@@ -13,7 +13,7 @@
 //   FLOPS, scale()      kernel_functions.hpp FLOPS() / uKerScaleFactor
 //   pack(rec, x, n, f)  build the LDS record of one source from the AoS inputs
 //   pair<R,MODE,MASKED>(acc, d, rec, ctx, K)   one pair interaction, d = x_trg - x_src  (generic-kernel.txx:83)
-// and the multi-density forms used by sctl_amd/csrc/multi_kernel.hpp (M densities on the same sources and targets):
+// and the multi-density forms used by sctl_amd/csrc/rows_kernel.hpp, forward (M densities on the same sources and targets):
 //   NREC_M<M>                  reals per LDS record: x, the normal where ND > 0, then M densities of K0 reals (pack_multi), padded to 16 bytes
 //   pack_m<R,M>(rec, x, n, f)  f[M][K0]: the record holds the geometry once and the densities as they are (no density is pre-multiplied
 //                              into the geometry: a double-layer record keeps n and applies each f in pair_m)
@@ -27,7 +27,7 @@
 //   pair_t<R,MODE,MASKED[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[k0] += sum_k1 U(d, n)[k0][k1] w[k1] with the SAME d = x_trg - x_src as pair(), n the owner's
 //                              normal (R[3], or R[1] unused when ND == 0) from registers.  Same rsqrt helpers, modes, masking and acc_factor as pair().
 //   finish_t<R>(acc) / finish_t_mode<R,MODE>(acc)   optional, applied once to a source's K0 sums (FinishTOf)
-// and the transposed forms for several weight vectors used by sctl_amd/csrc/multi_transpose_kernel.hpp (M weight vectors on the same targets and sources):
+// and the transposed forms for several weight vectors used by sctl_amd/csrc/rows_kernel.hpp, transposed (M weight vectors on the same targets and sources):
 //   NREC_TM<M>                 reals per streamed target record: x_t once, then what the pair needs of each of the M weight vectors, padded to 16 bytes
 //   pack_tm<R,M>(rec, x_t, w)  w[M][K1]: the weights as they are (the traction kernel: the six symmetric sums of each); nothing mode-dependent is folded in
 //   pair_tm<R,MODE,MASKED,M[,VARIANT]>(acc, d, n, rec, ctx, K)   acc[M][K0]: what does not depend on w (distance, reciprocal square root and its refinement,

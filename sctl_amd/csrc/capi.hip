@@ -1,7 +1,7 @@
 // C ABI of libsctl_amd.so (include/sctl_amd.h): the kernel registry and plugin loading, the error text, the shared argument checks, init / finalize,
 // the info and plan queries, and the device-pointer entries (checks + one driver call of eval_drivers.hpp).  The host-buffer entries are in
-// host_entries.hip, the operator handle in op.hip.  All arithmetic lives in eval_kernel.hpp / multi_kernel.hpp /
-// multi_transpose_kernel.hpp / ukernels.hpp.
+// host_entries.hip, the operator handle in op.hip.  All arithmetic lives in eval_kernel.hpp / rows_kernel.hpp /
+// ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -162,6 +162,28 @@ int check_grad_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int
   if (g_nrm && k->nd == 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string(k->name) + " has no source normal: g_nrm must be null");
   if (!has_grad(*k)) return no_grad(*k);
   return SCTL_AMD_OK;
+}
+// The passes of a call of nd >= 2 rows as the driver makes them (eval_drivers.hip): the first pass is the widest and gives the rows per pass, the owners per
+// lane, the splits and the workgroups of all its owner launches; the workspace is the largest any pass asks for.
+template <class Dir>
+void rows_passes_plan(const KernelEntry& k, const RowsEntry<Dir>& me, int real, int nd, int64_t Nt, int64_t Ns, int* rows_per_pass, int* passes, int* own_per_lane,
+                      int* splits, int64_t* workgroups, int64_t* workspace_bytes) {
+  constexpr bool FWD = std::is_same<Dir, RowsFwd>::value;
+  for (int m0 = 0; m0 < nd;) {
+    const int left = nd - m0;
+    const RowsPlan p = make_plan_multi(k, me, multi_form(me, left), real, FWD && Nt <= 0 ? 1 : Nt, !FWD && Ns <= 0 ? 1 : Ns);   // (an owner set is never planned empty)
+    if (*passes == 0) {
+      *rows_per_pass = p.M; *own_per_lane = p.T; *splits = p.splits;
+      const int64_t owners = FWD ? Nt : Ns, per_wg = (int64_t)kBlock * p.T;
+      for (int64_t o0 = 0; o0 < owners; o0 += p.owners_per_launch) {
+        const int64_t n = (owners - o0 < p.owners_per_launch) ? owners - o0 : p.owners_per_launch;
+        *workgroups += (n + per_wg - 1) / per_wg * p.splits;
+      }
+    }
+    *workspace_bytes = p.workspace_bytes > *workspace_bytes ? p.workspace_bytes : *workspace_bytes;
+    (*passes)++;
+    m0 += left < p.M ? left : p.M;
+  }
 }
 }  // namespace sctl_amd
 
@@ -324,27 +346,13 @@ int sctl_amd_eval_densities_plan(int kernel, int real, int nd, int64_t Nt, int64
   if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of densities");
   int dpp = 0, np = 0, t = 0, s = 0;
   int64_t wg = 0, ws = 0;
-  const MultiEntry* me = multi_entry(k->id);
+  const MultiEntry* me = multi_entry<RowsFwd>(k->id);
   if (nd == 1 || (nd > 1 && !me)) {   // the single-density plan, once per density
     const int rc = sctl_amd_eval_plan(kernel, real, Nt, Ns, Nt, digits, &t, &s, &wg, &ws);
     if (rc) return rc;
     dpp = 1; np = nd;
   } else if (nd > 1) {
-    // the first pass is the widest; the workspace is the largest any pass asks for
-    for (int m0 = 0; m0 < nd;) {
-      const int left = nd - m0;
-      const MultiPlan p = make_plan_multi(*k, *me, multi_form(*me, left), real, Nt > 0 ? Nt : 1, Ns);
-      if (np == 0) {
-        dpp = p.M; t = p.T; s = p.splits;
-        for (int64_t t0 = 0; t0 < Nt; t0 += p.nt_launch) {   // workgroups of all target launches of the pass
-          const int64_t n = (Nt - t0 < p.nt_launch) ? Nt - t0 : p.nt_launch;
-          wg += (n + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T) * p.splits;
-        }
-      }
-      ws = p.workspace_bytes > ws ? p.workspace_bytes : ws;
-      np++;
-      m0 += left < p.M ? left : p.M;
-    }
+    rows_passes_plan(*k, *me, real, nd, Nt, Ns, &dpp, &np, &t, &s, &wg, &ws);
   }
   if (densities_per_pass) *densities_per_pass = dpp;
   if (passes) *passes = np;
@@ -398,7 +406,7 @@ int sctl_amd_eval_transpose_densities_plan(int kernel, int real, int nd, int64_t
   (void)digits;   // every accuracy mode runs the same launch geometry
   int vpp = 0, np = 0, t = 0, s = 0;
   int64_t wg = 0, ws = 0;
-  const MultiTEntry* me = multi_t_entry(k->id);
+  const MultiTEntry* me = multi_entry<RowsTrans>(k->id);
   if (nd == 1 || (nd > 1 && !me)) {   // the single transposed plan, once per weight vector
     const PlanT p = make_plan_t(*k, real, Nt, Ns);
     const int64_t group = (int64_t)kBlock * kTTvalues[p.t_idx];
@@ -408,21 +416,7 @@ int sctl_amd_eval_transpose_densities_plan(int kernel, int real, int nd, int64_t
       wg += (n + group - 1) / group * p.splits;
     }
   } else if (nd > 1) {
-    // the first pass is the widest; the workspace is the largest any pass asks for
-    for (int m0 = 0; m0 < nd;) {
-      const int left = nd - m0;
-      const MultiTPlan p = make_plan_multi_t(*k, *me, multi_t_form(*me, left), real, Nt, Ns > 0 ? Ns : 1);
-      if (np == 0) {
-        vpp = p.M; t = p.T; s = p.splits;
-        for (int64_t s0 = 0; s0 < Ns; s0 += p.ns_launch) {   // workgroups of all source launches of the pass
-          const int64_t n = (Ns - s0 < p.ns_launch) ? Ns - s0 : p.ns_launch;
-          wg += (n + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T) * p.splits;
-        }
-      }
-      ws = p.workspace_bytes > ws ? p.workspace_bytes : ws;
-      np++;
-      m0 += left < p.M ? left : p.M;
-    }
+    rows_passes_plan(*k, *me, real, nd, Nt, Ns, &vpp, &np, &t, &s, &wg, &ws);
   }
   if (vectors_per_pass) *vectors_per_pass = vpp;
   if (passes) *passes = np;

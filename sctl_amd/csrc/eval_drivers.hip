@@ -1,6 +1,6 @@
 // Launch planning and the typed launch drivers of the all-pairs evaluators, behind the untyped functions of eval_drivers.hpp: the forward sum, several
 // densities, the transposed sum, several weight vectors through it, the geometry gradients and the kernel matrix.  All arithmetic lives in eval_kernel.hpp /
-// multi_kernel.hpp / multi_transpose_kernel.hpp / multi_grad_kernel.hpp / ukernels.hpp.
+// rows_kernel.hpp (several rows, both directions) / multi_grad_kernel.hpp / ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -332,151 +332,37 @@ int matrix_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, cons
 }
 }  // namespace
 
-// ---- several densities against one geometry (sctl_amd_eval_densities_*, multi_kernel.hpp) ----------------------------------------------
-// Launch table of the multi-density forms: the built-in kernels only; a registered plugin kernel has none (null) and is evaluated one density at a time.
-const MultiEntry* multi_entry(int kernel_id) {
+// ---- several rows through the all-pairs sum, forward and transposed (sctl_amd_eval_densities_*, sctl_amd_eval_transpose_densities_*, rows_kernel.hpp) --------
+// Launch tables of the several-row forms: the built-in kernels only; a registered plugin kernel has none (null) and is evaluated one row at a time.
+template <> const MultiEntry* multi_entry<RowsFwd>(int kernel_id) {
   static const MultiEntry* tab[SCTL_AMD_NUM_KERNELS] = {
       &multi_Laplace3D_FxU(), &multi_Laplace3D_DxU(), &multi_Laplace3D_FxdU(),  &multi_Stokes3D_FxU(),      &multi_Stokes3D_DxU(),
       &multi_Stokes3D_FxT(),  &multi_Stokes3D_FSxU(), &multi_Stokes3D_FxUP(), &multi_Laplace3D_FDxUdU(), &multi_Helmholtz3D_FxU()};
   return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
 }
-// the form for `left` densities still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
-int multi_form(const MultiEntry& me, int left) {
-  for (int i = 0; i < kNumMultiM; i++)
-    if (me.t[i] && (kMultiM[i] >= left || kMultiM[i] == me.m_max)) return i;
-  return 0;
-}
-constexpr int64_t kMultiWorkspaceCap = (int64_t)2 << 30;   // partial sums of one launch, [M][splits][Nt*K1]
-
-// make_plan with M densities per source: the same workgroup target, the L2 rule counting all M densities in a split's source bytes, and the
-// splits always in eights from 8 on (the XCD-owned mapping).  Partial sums [M][splits][nt*K1] stay within 2 GB by cutting the targets into
-// several launches, never by dropping below the L2 rule's split count.
-MultiPlan make_plan_multi(const KernelEntry& k, const MultiEntry& me, int form, int real, int64_t Nt, int64_t Ns) {
-  MultiPlan p{};
-  p.form = form; p.M = kMultiM[form]; p.T = me.t[form];
-  const int64_t rs = (int64_t)real_size(real), per_wg = (int64_t)kBlock * p.T;
-  const int64_t ntile = (Ns + kTile - 1) / kTile;
-  int64_t l2 = 1;
-  if ((double)Nt * (double)Ns >= 17179869184.0) {
-    const int64_t src_bytes = Ns * (3 + k.nd + (int64_t)p.M * k.k0) * rs;
-    l2 = (src_bytes + (2 << 20) - 1) / (2 << 20);
-    l2 = (l2 + 7) / 8 * 8;
-    if (l2 > 64) l2 = 64;
-  }
-  auto geometry = [&](int64_t nt) {
-    p.nt_launch = nt;
-    p.wg_x = (nt + per_wg - 1) / per_wg;
-    const int64_t want = (int64_t)cu_count() * ((double)nt * (double)Ns < 2147483648.0 ? 4 : 8);
-    int64_t s = (want + p.wg_x - 1) / p.wg_x;
-    if (s > 1024) s = 1024;
-    if (s < l2) s = l2;
-    if (s > ntile) s = ntile;
-    if (s < 1) s = 1;
-    const int64_t tiles_per = (ntile + s - 1) / s;
-    p.chunk = (tiles_per > 0 ? tiles_per : 1) * kTile;
-    int64_t splits = (Ns + p.chunk - 1) / p.chunk;
-    if (splits >= 8) splits = (splits + 7) / 8 * 8;   // (the splits past the sources have no work)
-    p.splits = (int)(splits < 1 ? 1 : splits);
-    p.workspace_bytes = p.splits > 1 ? (int64_t)p.M * p.splits * nt * k.k1 * rs : 0;
-  };
-  p.launches = 1;
-  for (;;) {
-    int64_t nt = (Nt + p.launches - 1) / p.launches;
-    nt = (nt + per_wg - 1) / per_wg * per_wg;
-    if (nt > Nt) nt = Nt;
-    geometry(nt);
-    if (p.workspace_bytes <= kMultiWorkspaceCap || nt <= per_wg) break;
-    const int64_t more = (p.workspace_bytes + kMultiWorkspaceCap - 1) / kMultiWorkspaceCap * p.launches;   // (at least one more launch)
-    p.launches = more > p.launches ? more : p.launches + 1;
-  }
-  p.launches = (Nt + p.nt_launch - 1) / p.nt_launch;
-  return p;
-}
-
-namespace {
-// nd >= 2 densities, density-major, on the device: passes of the widest form, the last pass on the narrowest form that takes what is left (a
-// single density left over runs on the 2-density form, so that every pass keeps this planner's 2 GB bound).  v is accumulated into.
-// A plugin kernel has no multi-density form: its densities go one at a time through the single-density path.
-template <class R>
-int eval_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits,
-                            const void* ctx, hipStream_t st, int64_t nt_whole = 0, bool presorted = false) {
-  if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
-  const int64_t f_stride = Ns * k.k0, v_stride = Nt * k.k1;
-  const MultiEntry* me = multi_entry(k.id);
-  const int mode = mode_for(real, digits);
-  for (int m0 = 0; m0 < nd;) {
-    const int left = nd - m0;
-    if (!me) {
-      const int rc = eval_device_t<R>(k, real, Nt, Ns, xt, xs, xn, f + m0 * f_stride, v + m0 * v_stride, digits, ctx, st, nt_whole, presorted);
-      if (rc) return rc;
-      m0++;
-      continue;
-    }
-    (void)hipGetLastError();
-    const MultiPlan p = make_plan_multi(k, *me, multi_form(*me, left), real, Nt, Ns);
-    const int nact = left < p.M ? left : p.M;
-    MultiArgs<R> a{};
-    a.Ns = Ns; a.xs = xs; a.xn = xn; a.f = f + m0 * f_stride; a.f_stride = f_stride; a.v_stride = v_stride;
-    a.chunk = p.chunk; a.nact = nact; a.scale = (R)(k.scale / k.acc_factor[mode]); a.ctx = make_ctx(k, ctx);
-    if (p.splits > 1) {
-      void* ws = nullptr;
-      HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
-      a.partial = (R*)ws;
-    }
-    MultiLaunch<R> launch;
-    if constexpr (std::is_same<R, double>::value) launch = me->f64[mode][p.form];
-    else launch = me->f32[mode][p.form];
-    for (int64_t t0 = 0; t0 < Nt; t0 += p.nt_launch) {
-      const int64_t nt = (Nt - t0 < p.nt_launch) ? Nt - t0 : p.nt_launch;
-      a.Nt = nt; a.xt = xt + t0 * 3; a.v_trg = v + m0 * v_stride + t0 * k.k1;
-      const dim3 grid((unsigned)((nt + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T)), (unsigned)p.splits);
-      launch(a, grid, st);
-      HIP_TRY(hipGetLastError());
-      if (p.splits > 1) {
-        const int64_t n = nt * k.k1;
-        for (int m = 0; m < nact; m++)
-          hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.v_trg + m * v_stride,
-                             (const R*)(a.partial + (int64_t)m * p.splits * n), n, p.splits, a.scale);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    count_work((int64_t)nact * Nt * Ns, k);
-    m0 += nact;
-  }
-  return SCTL_AMD_OK;
-}
-}  // namespace
-
-// ---- several weight vectors through the transposed sum (sctl_amd_eval_transpose_densities_*, multi_transpose_kernel.hpp) -----------------
-const MultiTEntry* multi_t_entry(int kernel_id) {
+template <> const MultiTEntry* multi_entry<RowsTrans>(int kernel_id) {
   static const MultiTEntry* tab[SCTL_AMD_NUM_KERNELS] = {
       &multi_t_Laplace3D_FxU(), &multi_t_Laplace3D_DxU(), &multi_t_Laplace3D_FxdU(),  &multi_t_Stokes3D_FxU(),      &multi_t_Stokes3D_DxU(),
       &multi_t_Stokes3D_FxT(),  &multi_t_Stokes3D_FSxU(), &multi_t_Stokes3D_FxUP(), &multi_t_Laplace3D_FDxUdU(), &multi_t_Helmholtz3D_FxU()};
   return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
 }
-int multi_t_form(const MultiTEntry& me, int left) {
-  for (int i = 0; i < kNumMultiTM; i++)
-    if (me.t[i] && (kMultiTM[i] >= left || kMultiTM[i] == me.m_max)) return i;
-  return 0;
-}
 
-MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int form, int real, int64_t Nt, int64_t Ns) {
-  MultiTPlan p{};
-  p.form = form; p.M = kMultiTM[form]; p.T = me.t[form];
-  const int64_t rs = (int64_t)real_size(real), per_wg = (int64_t)kBlock * p.T;
-  const int64_t ntile = (Nt + kTile - 1) / kTile;
-  const int64_t cap = transpose_workspace_cap();
+RowsPlan make_plan_rows(int form, int T, int64_t owners, int64_t streamed, int64_t streamed_reals, int64_t out_width, int64_t rs, int64_t cap) {
+  RowsPlan p{};
+  p.form = form; p.M = kRowsM[form]; p.T = T;
+  const int64_t per_wg = (int64_t)kBlock * p.T;
+  const int64_t ntile = (streamed + kTile - 1) / kTile;
   int64_t l2 = 1;
-  if ((double)Nt * (double)Ns >= 17179869184.0) {   // one split's streamed data, all M weight vectors of a target with it, <= 2 MB
-    const int64_t trg_bytes = Nt * (3 + (int64_t)p.M * k.k1) * rs;
-    l2 = (trg_bytes + (2 << 20) - 1) / (2 << 20);
+  if ((double)owners * (double)streamed >= 17179869184.0) {   // one split's streamed data, all M rows of a point with it, <= 2 MB
+    const int64_t bytes = streamed * streamed_reals * rs;
+    l2 = (bytes + (2 << 20) - 1) / (2 << 20);
     l2 = (l2 + 7) / 8 * 8;
     if (l2 > 64) l2 = 64;
   }
-  auto geometry = [&](int64_t ns) {
-    p.ns_launch = ns;
-    p.wg_x = (ns + per_wg - 1) / per_wg;
-    const int64_t want = (int64_t)cu_count() * ((double)ns * (double)Nt < 2147483648.0 ? 4 : 8);
+  auto geometry = [&](int64_t n) {
+    p.owners_per_launch = n;
+    p.wg_x = (n + per_wg - 1) / per_wg;
+    const int64_t want = (int64_t)cu_count() * ((double)n * (double)streamed < 2147483648.0 ? 4 : 8);
     int64_t s = (want + p.wg_x - 1) / p.wg_x;
     if (s > 1024) s = 1024;
     if (s < l2) s = l2;
@@ -484,67 +370,79 @@ MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int fo
     if (s < 1) s = 1;
     const int64_t tiles_per = (ntile + s - 1) / s;
     p.chunk = (tiles_per > 0 ? tiles_per : 1) * kTile;
-    int64_t splits = (Nt + p.chunk - 1) / p.chunk;
-    if (splits >= 8) splits = (splits + 7) / 8 * 8;   // (the splits past the targets have no work)
+    int64_t splits = (streamed + p.chunk - 1) / p.chunk;
+    if (splits >= 8) splits = (splits + 7) / 8 * 8;   // (the splits past the streamed points have no work)
     p.splits = (int)(splits < 1 ? 1 : splits);
-    p.workspace_bytes = p.splits > 1 ? (int64_t)p.M * p.splits * ns * k.k0 * rs : 0;
+    p.workspace_bytes = p.splits > 1 ? (int64_t)p.M * p.splits * n * out_width * rs : 0;
   };
   p.launches = 1;
   for (;;) {
-    int64_t ns = (Ns + p.launches - 1) / p.launches;
-    ns = (ns + per_wg - 1) / per_wg * per_wg;
-    if (ns > Ns) ns = Ns;
-    geometry(ns);
-    if (p.workspace_bytes <= cap || ns <= per_wg) break;
+    int64_t n = (owners + p.launches - 1) / p.launches;
+    n = (n + per_wg - 1) / per_wg * per_wg;
+    if (n > owners) n = owners;
+    geometry(n);
+    if (p.workspace_bytes <= cap || n <= per_wg) break;
     const int64_t more = (p.workspace_bytes + cap - 1) / cap * p.launches;   // (at least one more launch)
     p.launches = more > p.launches ? more : p.launches + 1;
   }
-  p.launches = (Ns + p.ns_launch - 1) / p.ns_launch;
+  p.launches = (owners + p.owners_per_launch - 1) / p.owners_per_launch;
   return p;
 }
+constexpr int64_t kMultiWorkspaceCap = (int64_t)2 << 30;   // partial sums of one forward launch, [M][splits][nt*K1]: fixed, no variable lowers it
+template <class Dir> RowsPlan make_plan_multi(const KernelEntry& k, const RowsEntry<Dir>& me, int form, int real, int64_t Nt, int64_t Ns) {
+  const int64_t M = kRowsM[form], rs = (int64_t)real_size(real);
+  if constexpr (std::is_same<Dir, RowsFwd>::value) return make_plan_rows(form, me.t[form], Nt, Ns, 3 + k.nd + M * k.k0, k.k1, rs, kMultiWorkspaceCap);
+  else return make_plan_rows(form, me.t[form], Ns, Nt, 3 + M * k.k1, k.k0, rs, transpose_workspace_cap());
+}
+template RowsPlan make_plan_multi<RowsFwd>(const KernelEntry&, const MultiEntry&, int, int, int64_t, int64_t);
+template RowsPlan make_plan_multi<RowsTrans>(const KernelEntry&, const MultiTEntry&, int, int, int64_t, int64_t);
 
 namespace {
-// nd >= 2 weight vectors, row-major, on the device: passes of the widest form, the last pass on the narrowest form that takes what is left, as
-// eval_densities_device_t.  g is accumulated into.  A plugin kernel with pair_t has no pair_tm: its rows go one at a time through the single path.
-template <class R>
-int eval_transpose_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* w, R* g,
-                                      int digits, const void* ctx, hipStream_t st) {
+// nd >= 2 rows, row-major, on the device, in either direction (in: the densities f forward, the weights w transposed; out: v and g): passes of the widest form,
+// the last pass on the narrowest form that takes what is left (a single row left over runs on the form of 2, so that every pass keeps this planner's bound).  out
+// is accumulated into.  A plugin kernel has no several-row form: `single(in_row, out_row)` sends its rows one at a time through the single-row driver.
+template <class Dir, class R, class Single>
+int eval_rows_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* in, R* out, int digits,
+                       const void* ctx, hipStream_t st, Single single) {
   if (nd == 0 || Nt == 0 || Ns == 0) return SCTL_AMD_OK;
-  const int64_t w_stride = Nt * k.k1, g_stride = Ns * k.k0;
-  const MultiTEntry* me = multi_t_entry(k.id);
+  constexpr bool FWD = std::is_same<Dir, RowsFwd>::value;
+  const int64_t owners = FWD ? Nt : Ns, kout = FWD ? k.k1 : k.k0;
+  const int64_t in_stride = FWD ? Ns * k.k0 : Nt * k.k1, out_stride = owners * kout;
+  const RowsEntry<Dir>* me = multi_entry<Dir>(k.id);
   const int mode = mode_for(real, digits);
   for (int m0 = 0; m0 < nd;) {
     const int left = nd - m0;
     if (!me) {
-      const int rc = eval_transpose_device_t<R>(k, real, Nt, Ns, xt, xs, xn, w + m0 * w_stride, g + m0 * g_stride, digits, ctx, st);
+      const int rc = single(in + m0 * in_stride, out + m0 * out_stride);
       if (rc) return rc;
       m0++;
       continue;
     }
     (void)hipGetLastError();
-    const MultiTPlan p = make_plan_multi_t(k, *me, multi_t_form(*me, left), real, Nt, Ns);
+    const RowsPlan p = make_plan_multi(k, *me, multi_form(*me, left), real, Nt, Ns);
     const int nact = left < p.M ? left : p.M;
-    MultiTArgs<R> a{};
-    a.Nt = Nt; a.xt = xt; a.w = w + m0 * w_stride; a.w_stride = w_stride; a.g_stride = g_stride;
+    RowsArgs<R> a{};
+    a.n_str = FWD ? Ns : Nt; a.x_str = FWD ? xs : xt; a.in = in + m0 * in_stride; a.in_stride = in_stride; a.out_stride = out_stride;
     a.chunk = p.chunk; a.nact = nact; a.scale = (R)(k.scale / k.acc_factor[mode]); a.ctx = make_ctx(k, ctx);
     if (p.splits > 1) {
       void* ws = nullptr;
       HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
       a.partial = (R*)ws;
     }
-    MultiTLaunch<R> launch;
+    RowsLaunch<R> launch;
     if constexpr (std::is_same<R, double>::value) launch = me->f64[mode][p.form];
     else launch = me->f32[mode][p.form];
-    for (int64_t s0 = 0; s0 < Ns; s0 += p.ns_launch) {   // one launch unless the partial sums of all owners would pass the bound
-      const int64_t ns = (Ns - s0 < p.ns_launch) ? Ns - s0 : p.ns_launch;
-      a.Ns = ns; a.xs = xs + s0 * 3; a.xn = xn ? xn + s0 * k.nd : nullptr; a.g_src = g + m0 * g_stride + s0 * k.k0;
-      const dim3 grid((unsigned)((ns + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T)), (unsigned)p.splits);
+    for (int64_t o0 = 0; o0 < owners; o0 += p.owners_per_launch) {   // one launch unless the partial sums of all owners would pass the bound
+      const int64_t no = (owners - o0 < p.owners_per_launch) ? owners - o0 : p.owners_per_launch;
+      a.n_own = no; a.x_own = (FWD ? xt : xs) + o0 * 3; a.out = out + m0 * out_stride + o0 * kout;
+      a.nrm = (FWD || !xn) ? xn : xn + o0 * k.nd;   // the normals are the sources': they advance with the owner cut only where the sources own
+      const dim3 grid((unsigned)((no + (int64_t)kBlock * p.T - 1) / ((int64_t)kBlock * p.T)), (unsigned)p.splits);
       launch(a, grid, st);
       HIP_TRY(hipGetLastError());
       if (p.splits > 1) {
-        const int64_t n = ns * k.k0;
+        const int64_t n = no * kout;
         for (int m = 0; m < nact; m++)
-          hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.g_src + m * g_stride,
+          hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.out + m * out_stride,
                              (const R*)(a.partial + (int64_t)m * p.splits * n), n, p.splits, a.scale);
         HIP_TRY(hipGetLastError());
       }
@@ -553,6 +451,20 @@ int eval_transpose_densities_device_t(const KernelEntry& k, int real, int nd, in
     m0 += nact;
   }
   return SCTL_AMD_OK;
+}
+template <class R>
+int eval_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, R* v, int digits,
+                            const void* ctx, hipStream_t st, int64_t nt_whole = 0, bool presorted = false) {
+  return eval_rows_device_t<RowsFwd, R>(k, real, nd, Nt, Ns, xt, xs, xn, f, v, digits, ctx, st, [&](const R* fm, R* vm) {
+    return eval_device_t<R>(k, real, Nt, Ns, xt, xs, xn, fm, vm, digits, ctx, st, nt_whole, presorted);
+  });
+}
+template <class R>
+int eval_transpose_densities_device_t(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* w, R* g,
+                                      int digits, const void* ctx, hipStream_t st) {
+  return eval_rows_device_t<RowsTrans, R>(k, real, nd, Nt, Ns, xt, xs, xn, w, g, digits, ctx, st, [&](const R* wm, R* gm) {
+    return eval_transpose_device_t<R>(k, real, Nt, Ns, xt, xs, xn, wm, gm, digits, ctx, st);
+  });
 }
 }  // namespace
 

@@ -2,8 +2,7 @@
 // stream; the typed templates behind it are private to eval_drivers.hip.
 #pragma once
 #include "internal.hpp"
-#include "multi_kernel.hpp"
-#include "multi_transpose_kernel.hpp"
+#include "rows_kernel.hpp"
 #include "multi_grad_kernel.hpp"
 
 namespace sctl_amd {
@@ -51,26 +50,28 @@ struct PlanOwned {
 PlanOwned plan_owned(int64_t owners, int64_t streamed, int t, int64_t streamed_reals, int64_t out_width, int64_t rs);
 PlanOwned make_plan_g(const KernelEntry& k, int real, int side, int64_t Nt, int64_t Ns);
 
-// ---- several densities against one geometry (multi_kernel.hpp) ----
-const MultiEntry* multi_entry(int kernel_id);   // null for a registered plugin kernel: it is evaluated one density at a time
-int multi_form(const MultiEntry& me, int left); // the form for `left` densities still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
-struct MultiPlan {
+// ---- several rows through the all-pairs sum: densities forward (Dir = RowsFwd), weight vectors transposed (RowsTrans); rows_kernel.hpp ----
+template <class Dir> const RowsEntry<Dir>* multi_entry(int kernel_id);   // null for a registered plugin kernel: its rows go one at a time through the single-row path
+template <> const MultiEntry* multi_entry<RowsFwd>(int kernel_id);
+template <> const MultiTEntry* multi_entry<RowsTrans>(int kernel_id);
+// the form for `left` rows still to do: the narrowest of 2 / 4 / 8 that takes them all, else the widest
+template <class Dir> int multi_form(const RowsEntry<Dir>& me, int left) {
+  for (int i = 0; i < kNumRowsM; i++)
+    if (me.t[i] && (kRowsM[i] >= left || kRowsM[i] == me.m_max)) return i;
+  return 0;
+}
+// make_plan with M rows in a streamed record, in terms of owners (the targets forward, the sources transposed) and streamed points: the same workgroup target, the
+// L2 rule counting all `streamed_reals` of a record in a split's streamed bytes, and the splits always in eights from 8 on (the XCD-owned mapping).  The partial
+// sums [M][splits][owners_per_launch * out_width] stay within `cap` bytes by cutting the owners into launches of whole workgroups, never by dropping below the L2
+// rule's split count: the splits are what keeps a streamed chunk in one XCD's L2.
+struct RowsPlan {
   int form, M, T, splits;
-  int64_t chunk, nt_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the targets of one launch of nt_launch targets
+  int64_t chunk, owners_per_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the owners of one launch of owners_per_launch owners
 };
-MultiPlan make_plan_multi(const KernelEntry& k, const MultiEntry& me, int form, int real, int64_t Nt, int64_t Ns);
-
-// ---- several weight vectors through the transposed sum (multi_transpose_kernel.hpp) ----
-const MultiTEntry* multi_t_entry(int kernel_id);    // null for a registered plugin kernel: its rows go one at a time through the single transposed path
-int multi_t_form(const MultiTEntry& me, int left);  // as multi_form
-// make_plan_multi with the point sets exchanged: the SOURCES own the sums and tile grid.x, the TARGET range is split; the L2 rule counts all M weight
-// vectors in a split's streamed bytes, the splits come in eights from 8 on, and the partial sums [M][splits][ns_launch * K0] stay within 2 GB (or what
-// SCTL_AMD_TRANSPOSE_WORKSPACE lowers that to) by cutting the owners into launches of whole workgroups, never by taking fewer splits.
-struct MultiTPlan {
-  int form, M, T, splits;
-  int64_t chunk, ns_launch, launches, wg_x, workspace_bytes;   // wg_x: workgroups along the sources of one launch of ns_launch sources
-};
-MultiTPlan make_plan_multi_t(const KernelEntry& k, const MultiTEntry& me, int form, int real, int64_t Nt, int64_t Ns);
+RowsPlan make_plan_rows(int form, int T, int64_t owners, int64_t streamed, int64_t streamed_reals, int64_t out_width, int64_t rs, int64_t cap);
+// ... of one direction.  Forward: a streamed source brings its normal and M densities, and the bound is a fixed 2 GB.  Transposed: a streamed target brings M
+// weight vectors, and SCTL_AMD_TRANSPOSE_WORKSPACE may lower the bound of 2 GB (it never touches the forward plan).
+template <class Dir> RowsPlan make_plan_multi(const KernelEntry& k, const RowsEntry<Dir>& me, int form, int real, int64_t Nt, int64_t Ns);
 
 // ---- geometry gradients for several density / weight rows (multi_grad_kernel.hpp) ----
 const MultiGEntry* multi_g_entry(int kernel_id);    // null for a registered plugin kernel: its rows go one at a time through the single gradient path

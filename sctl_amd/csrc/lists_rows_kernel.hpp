@@ -19,11 +19,12 @@
 // fp32 runs this exact vector-pipe pair at every accuracy, as eval_multi_kernel and every transposed kernel do.
 //
 // The two directions differ only in the policy `Dir` (ListFwd, ListTrans below): which of K0 / K1 is the output width, the record, who carries the normal, the
-// sign of d, and the names of the fields of ListArgs / ListTArgs.  Everything else — the walker, the form, the dispatch, the launch table — exists once.
+// sign of d (rows_dir.hpp), and the names of the fields of ListArgs / ListTArgs.  Everything else — the walker, the form, the dispatch, the launch table — exists once.
 #pragma once
 #include <sctl_amd/device/launch.hpp>
 #include <sctl_amd/device/lists_kernel.hpp>
 #include <sctl_amd/device/lists_transpose_kernel.hpp>
+#include "rows_dir.hpp"
 
 namespace sctl_amd {
 
@@ -37,58 +38,29 @@ template <class L> struct ListRowsArgs {
 template <class R> using ListMultiArgs = ListRowsArgs<ListArgs<R>>;
 template <class R> using ListMultiTArgs = ListRowsArgs<ListTArgs<R>>;
 
-// Forward: the owners are the targets; sources are streamed with their normal and M densities of K0 reals; a target gathers M x K1 sums.
-struct ListFwd {
+// The direction-only half of the policy (widths, record, pack, pair, finish) is RowsFwd / RowsTrans of rows_dir.hpp, shared with the all-pairs kernels; what is
+// added here is about ListArgs / ListTArgs.  Forward: the owners are the targets.
+struct ListFwd : RowsFwd {
   static constexpr int SIDE = 0;      // of sctl_amd_lists::side
   template <class R> using Args = ListMultiArgs<R>;
-  template <class Ker> static constexpr int KOUT = Ker::K1;      // reals of an output row per owner
-  template <class Ker> static constexpr int KIN = Ker::K0;       // reals of an input row per streamed point
-  template <class Ker> static constexpr int OWN_N = 0;           // reals of the normal an owner holds
-  template <class Ker> static constexpr int STR_N = Ker::ND;     // reals of the normal a streamed point brings
-  template <class Ker, int M> static constexpr int NREC = Ker::template NREC_M<M>;
   template <class R> static __device__ __forceinline__ const R* own_x(const ListArgs<R>& l) { return l.xt; }
   template <class R> static __device__ __forceinline__ const R* own_n(const ListArgs<R>&) { return nullptr; }
   template <class R> static __device__ __forceinline__ const R* str_x(const ListArgs<R>& l) { return l.xs; }
   template <class R> static __device__ __forceinline__ const R* str_n(const ListArgs<R>& l) { return l.xn; }
   template <class R> static __device__ __forceinline__ const R* in(const ListArgs<R>& l) { return l.f; }
   template <class R> static __device__ __forceinline__ R* out(const ListArgs<R>& l) { return l.v_trg; }
-  template <class Ker, class R, int M> static __device__ __forceinline__ void pack(R* rec, const R* x, const R* n, const R (&f)[M][Ker::K0]) {
-    Ker::template pack_m<R, M>(rec, x, n, f);
-  }
-  template <class Ker, class R, int MODE, bool MASKED, int M, int VARIANT, class KC>
-  static __device__ __forceinline__ void pair(R (&tacc)[M][Ker::K1], const R (&xt)[3], const R (&)[1], const R* rec, const KerCtx& ctx, const KC& K) {
-    const R d[3] = {xt[0] - rec[0], xt[1] - rec[1], xt[2] - rec[2]};
-    if constexpr (KC::HAS_VARIANT) Ker::template pair_m<R, MODE, MASKED, M, VARIANT>(tacc, d, rec, ctx, K);
-    else Ker::template pair_m<R, MODE, MASKED, M>(tacc, d, rec, ctx, K);
-  }
-  template <class Ker, class R, int MODE> static __device__ __forceinline__ void finish(R (&acc)[Ker::K1]) { finish_acc<Ker, R, MODE>(acc); }
 };
 
-// Transposed: the owners are the sources, each with its normal; targets are streamed with M weight vectors of K1 reals; a source gathers M x K0 sums.
-struct ListTrans {
+// Transposed: the owners are the sources, each with its normal.
+struct ListTrans : RowsTrans {
   static constexpr int SIDE = 1;
   template <class R> using Args = ListMultiTArgs<R>;
-  template <class Ker> static constexpr int KOUT = Ker::K0;
-  template <class Ker> static constexpr int KIN = Ker::K1;
-  template <class Ker> static constexpr int OWN_N = Ker::ND ? 3 : 0;
-  template <class Ker> static constexpr int STR_N = 0;
-  template <class Ker, int M> static constexpr int NREC = Ker::template NREC_TM<M>;
   template <class R> static __device__ __forceinline__ const R* own_x(const ListTArgs<R>& l) { return l.xs; }
   template <class R> static __device__ __forceinline__ const R* own_n(const ListTArgs<R>& l) { return l.xn; }
   template <class R> static __device__ __forceinline__ const R* str_x(const ListTArgs<R>& l) { return l.xt; }
   template <class R> static __device__ __forceinline__ const R* str_n(const ListTArgs<R>&) { return nullptr; }
   template <class R> static __device__ __forceinline__ const R* in(const ListTArgs<R>& l) { return l.w; }
   template <class R> static __device__ __forceinline__ R* out(const ListTArgs<R>& l) { return l.g_src; }
-  template <class Ker, class R, int M> static __device__ __forceinline__ void pack(R* rec, const R* x, const R*, const R (&w)[M][Ker::K1]) {
-    Ker::template pack_tm<R, M>(rec, x, w);
-  }
-  template <class Ker, class R, int MODE, bool MASKED, int M, int VARIANT, class KC>
-  static __device__ __forceinline__ void pair(R (&tacc)[M][Ker::K0], const R (&xs)[3], const R (&xn)[Ker::ND ? 3 : 1], const R* rec, const KerCtx& ctx, const KC& K) {
-    const R d[3] = {rec[0] - xs[0], rec[1] - xs[1], rec[2] - xs[2]};
-    if constexpr (KC::HAS_VARIANT) Ker::template pair_tm<R, MODE, MASKED, M, VARIANT>(tacc, d, xn, rec, ctx, K);
-    else Ker::template pair_tm<R, MODE, MASKED, M>(tacc, d, xn, rec, ctx, K);
-  }
-  template <class Ker, class R, int MODE> static __device__ __forceinline__ void finish(R (&acc)[Ker::K0]) { finish_t_acc<Ker, R, MODE>(acc); }
 };
 
 // A workgroup is ONE wave: two waves per SIMD are eight workgroups per CU, so a form may use an eighth of the CU's 160 KB of LDS.

@@ -1,8 +1,8 @@
-// Multi-density forms of Laplace3D_FxU (multi_kernel.hpp): targets per lane 2 / 2 / 2 for 2 / 4 / 8 densities.
-#include "multi_kernel.hpp"
+// Multi-density forms of Laplace3D_FxU (rows_kernel.hpp, forward): targets per lane 2 / 2 / 2 for 2 / 4 / 8 densities.
+#include "rows_kernel.hpp"
 namespace sctl_amd {
 const MultiEntry& multi_Laplace3D_FxU() {
-  static const MultiEntry e = make_multi_entry<Laplace3D_FxU, 2, 2, 2>();
+  static const MultiEntry e = make_rows_entry<RowsFwd, Laplace3D_FxU, 2, 2, 2>();
   return e;
 }
 }  // namespace sctl_amd

@@ -1,8 +1,8 @@
-// Multi-density forms of Stokes3D_DxU (multi_kernel.hpp): targets per lane 2 / 1 / 1 for 2 / 4 / 8 densities.
-#include "multi_kernel.hpp"
+// Multi-density forms of Stokes3D_DxU (rows_kernel.hpp, forward): targets per lane 2 / 1 / 1 for 2 / 4 / 8 densities.
+#include "rows_kernel.hpp"
 namespace sctl_amd {
 const MultiEntry& multi_Stokes3D_DxU() {
-  static const MultiEntry e = make_multi_entry<Stokes3D_DxU, 2, 1, 1>();
+  static const MultiEntry e = make_rows_entry<RowsFwd, Stokes3D_DxU, 2, 1, 1>();
   return e;
 }
 }  // namespace sctl_amd

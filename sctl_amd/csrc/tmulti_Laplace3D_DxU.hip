@@ -1,8 +1,8 @@
-// Transposed forms of Laplace3D_DxU for several weight vectors (multi_transpose_kernel.hpp): sources per lane 2 / 2 / 2 for 2 / 4 / 8 weight vectors.
-#include "multi_transpose_kernel.hpp"
+// Transposed forms of Laplace3D_DxU for several weight vectors (rows_kernel.hpp, transposed): sources per lane 2 / 2 / 2 for 2 / 4 / 8 weight vectors.
+#include "rows_kernel.hpp"
 namespace sctl_amd {
 const MultiTEntry& multi_t_Laplace3D_DxU() {
-  static const MultiTEntry e = make_multi_t_entry<Laplace3D_DxU, 2, 2, 2>();
+  static const MultiTEntry e = make_rows_entry<RowsTrans, Laplace3D_DxU, 2, 2, 2>();
   return e;
 }
 }  // namespace sctl_amd

@@ -1,8 +1,8 @@
-// Transposed forms of Stokes3D_FSxU for several weight vectors (multi_transpose_kernel.hpp): sources per lane 2 / 1 / 1 for 2 / 4 / 8 weight vectors.
-#include "multi_transpose_kernel.hpp"
+// Transposed forms of Stokes3D_FSxU for several weight vectors (rows_kernel.hpp, transposed): sources per lane 2 / 1 / 1 for 2 / 4 / 8 weight vectors.
+#include "rows_kernel.hpp"
 namespace sctl_amd {
 const MultiTEntry& multi_t_Stokes3D_FSxU() {
-  static const MultiTEntry e = make_multi_t_entry<Stokes3D_FSxU, 2, 1, 1>();
+  static const MultiTEntry e = make_rows_entry<RowsTrans, Stokes3D_FSxU, 2, 1, 1>();
   return e;
 }
 }  // namespace sctl_amd

@@ -106,6 +106,102 @@ def test_planner_cuts_the_targets_when_the_partial_sums_would_pass_2gb():
     assert pl["workgroups"] == -(-N // (256 * pl["trg_per_lane"])) * s
 
 
+# (kernel, real, nd, Nt, Ns, forward plan, transposed plan) with a plan as (rows per pass, passes, owners per lane, splits, workgroups, workspace bytes): what the
+# two separate planners (make_plan_multi, make_plan_multi_t) returned before they became one (make_plan_rows), SCTL_AMD_TRANSPOSE_WORKSPACE unset, 256 CUs.
+# Among them Stokes3D-FSxU fp64 with 8 rows at 2^22 x 2^22 in both directions, Stokes3D-FxT (widest form 4, owner cuts) and kernels with a source normal at
+# sizes where the forward L2 rule counts it (Laplace3D-DxU fp64, 4 rows, 2^20 x 2^20: 40 splits forward, 32 transposed).
+PLANS_BEFORE_THE_MERGE = (
+    ("Stokes3D-FSxU", 0, 8, 1 << 22, 1 << 22, (4, 2, 1, 64, 1048576, 1074266112), (8, 1, 1, 64, 1048576, 2147483648)),
+    ("Stokes3D-FxT", 0, 8, 1 << 20, 1 << 20, (4, 2, 1, 64, 262144, 1075838976), (4, 2, 1, 64, 262144, 1074266112)),
+    ("Stokes3D-FxT", 1, 8, 1 << 20, 1 << 20, (4, 2, 1, 32, 131072, 1611399168), (4, 2, 1, 64, 262144, 1610612736)),
+    ("Laplace3D-DxU", 0, 4, 1 << 20, 1 << 20, (4, 1, 2, 40, 81920, 1342177280), (4, 1, 2, 32, 65536, 1073741824)),
+    ("Stokes3D-DxU", 1, 8, 1 << 22, 1 << 22, (8, 1, 1, 64, 1048576, 1074266112), (8, 1, 1, 64, 1048576, 1074266112)),
+    ("Helmholtz3D-FxU", 0, 33, 1 << 22, 1 << 22, (8, 5, 1, 64, 1048576, 2147483648), (8, 5, 1, 64, 1048576, 2147483648)),
+    ("Laplace3D-FxU", 0, 2, 1, 1, (2, 1, 2, 1, 1, 0), (2, 1, 2, 1, 1, 0)),
+    ("Laplace3D-FxU", 1, 5, 1 << 12, 64, (8, 1, 2, 1, 8, 0), (8, 1, 2, 16, 16, 32768)),
+    ("Laplace3D-FxU", 0, 33, 1 << 20, 1 << 20, (8, 5, 2, 48, 98304, 1610612736), (8, 5, 2, 48, 98304, 1610612736)),
+    ("Laplace3D-FxU", 1, 4, 1 << 14, 1 << 23, (4, 1, 2, 64, 2048, 16777216), (4, 1, 2, 8, 131072, 1073741824)),
+    ("Laplace3D-FxU", 0, 11, 1000, 513, (8, 2, 2, 3, 6, 192000), (8, 2, 2, 4, 8, 131328)),
+    ("Laplace3D-FxU", 1, 3, 1 << 18, 1 << 18, (4, 1, 2, 8, 4096, 33554432), (4, 1, 2, 8, 4096, 33554432)),
+    ("Laplace3D-DxU", 1, 4, 1 << 22, 1 << 22, (4, 1, 2, 64, 524288, 2147483648), (4, 1, 2, 56, 458752, 1879048192)),
+    ("Laplace3D-DxU", 0, 11, 1, 1, (8, 2, 2, 1, 1, 0), (8, 2, 2, 1, 1, 0)),
+    ("Laplace3D-DxU", 1, 3, 1 << 12, 64, (4, 1, 2, 1, 8, 0), (4, 1, 2, 16, 16, 16384)),
+    ("Laplace3D-DxU", 0, 8, 1 << 20, 1 << 20, (8, 1, 2, 56, 114688, 1879048192), (8, 1, 2, 48, 98304, 1610612736)),
+    ("Laplace3D-DxU", 1, 2, 1 << 14, 1 << 23, (2, 1, 2, 64, 2048, 8388608), (2, 1, 2, 8, 131072, 536870912)),
+    ("Laplace3D-DxU", 0, 5, 1000, 513, (8, 1, 2, 3, 6, 192000), (8, 1, 2, 4, 8, 131328)),
+    ("Laplace3D-FxdU", 0, 8, 1 << 14, 1 << 14, (8, 1, 1, 16, 1024, 50331648), (8, 1, 1, 16, 1024, 16777216)),
+    ("Laplace3D-FxdU", 1, 2, 1 << 22, 1 << 22, (2, 1, 2, 40, 327680, 2013265920), (2, 1, 2, 64, 524288, 2147483648)),
+    ("Laplace3D-FxdU", 0, 5, 1, 1, (8, 1, 1, 1, 1, 0), (8, 1, 1, 1, 1, 0)),
+    ("Laplace3D-FxdU", 1, 33, 1 << 12, 64, (8, 5, 1, 1, 16, 0), (8, 5, 1, 16, 16, 32768)),
+    ("Laplace3D-FxdU", 0, 4, 1 << 20, 1 << 20, (4, 1, 1, 32, 131072, 1610612736), (4, 1, 1, 64, 262144, 2147483648)),
+    ("Laplace3D-FxdU", 1, 11, 1 << 14, 1 << 23, (8, 2, 1, 64, 4096, 100663296), (8, 2, 1, 8, 262144, 2147483648)),
+    ("Stokes3D-FxU", 1, 33, 300, 300, (8, 5, 1, 2, 4, 57600), (8, 5, 1, 2, 4, 57600)),
+    ("Stokes3D-FxU", 0, 4, 1 << 14, 1 << 14, (4, 1, 1, 16, 1024, 25165824), (4, 1, 1, 16, 1024, 25165824)),
+    ("Stokes3D-FxU", 1, 11, 1 << 22, 1 << 22, (8, 2, 1, 64, 1048576, 1074266112), (8, 2, 1, 64, 1048576, 1074266112)),
+    ("Stokes3D-FxU", 0, 3, 1, 1, (4, 1, 1, 1, 1, 0), (4, 1, 1, 1, 1, 0)),
+    ("Stokes3D-FxU", 1, 8, 1 << 12, 64, (8, 1, 1, 1, 16, 0), (8, 1, 1, 16, 16, 98304)),
+    ("Stokes3D-FxU", 0, 2, 1 << 20, 1 << 20, (2, 1, 2, 40, 81920, 2013265920), (2, 1, 2, 40, 81920, 2013265920)),
+    ("Stokes3D-DxU", 0, 3, 1 << 23, 1 << 14, (4, 1, 1, 8, 262144, 1073872896), (4, 1, 1, 64, 4096, 100663296)),
+    ("Stokes3D-DxU", 1, 8, 300, 300, (8, 1, 1, 2, 4, 57600), (8, 1, 1, 2, 4, 57600)),
+    ("Stokes3D-DxU", 0, 2, 1 << 14, 1 << 14, (2, 1, 2, 32, 1024, 25165824), (2, 1, 2, 32, 1024, 25165824)),
+    ("Stokes3D-DxU", 1, 5, 1 << 22, 1 << 22, (8, 1, 1, 64, 1048576, 1074266112), (8, 1, 1, 64, 1048576, 1074266112)),
+    ("Stokes3D-DxU", 0, 33, 1, 1, (8, 5, 1, 1, 1, 0), (8, 5, 1, 1, 1, 0)),
+    ("Stokes3D-DxU", 1, 4, 1 << 12, 64, (4, 1, 1, 1, 16, 0), (4, 1, 1, 16, 16, 49152)),
+    ("Stokes3D-FxT", 1, 5, 1 << 18, 1 << 18, (4, 2, 1, 8, 8192, 301989888), (4, 2, 1, 24, 24576, 301989888)),
+    ("Stokes3D-FxT", 0, 33, 1 << 23, 1 << 14, (4, 9, 1, 8, 262144, 1932853248), (4, 9, 1, 64, 4096, 100663296)),
+    ("Stokes3D-FxT", 1, 4, 300, 300, (4, 1, 1, 2, 4, 86400), (4, 1, 1, 2, 4, 28800)),
+    ("Stokes3D-FxT", 0, 11, 1 << 14, 1 << 14, (4, 3, 1, 16, 1024, 75497472), (4, 3, 1, 16, 1024, 25165824)),
+    ("Stokes3D-FxT", 1, 3, 1 << 22, 1 << 22, (4, 1, 1, 64, 1048576, 1075838976), (4, 1, 1, 64, 1048576, 1074266112)),
+    ("Stokes3D-FxT", 0, 8, 1, 1, (4, 2, 1, 1, 1, 0), (4, 2, 1, 1, 1, 0)),
+    ("Stokes3D-FSxU", 0, 11, 1000, 513, (4, 3, 1, 3, 12, 288000), (8, 2, 1, 4, 12, 525312)),
+    ("Stokes3D-FSxU", 1, 3, 1 << 18, 1 << 18, (4, 1, 1, 16, 16384, 201326592), (4, 1, 1, 8, 8192, 134217728)),
+    ("Stokes3D-FSxU", 0, 8, 1 << 23, 1 << 14, (4, 2, 1, 8, 262144, 1073872896), (8, 1, 1, 64, 4096, 268435456)),
+    ("Stokes3D-FSxU", 1, 2, 300, 300, (2, 1, 2, 2, 2, 14400), (2, 1, 2, 2, 2, 19200)),
+    ("Stokes3D-FSxU", 0, 5, 1 << 14, 1 << 14, (4, 2, 1, 16, 1024, 25165824), (8, 1, 1, 16, 1024, 67108864)),
+    ("Stokes3D-FSxU", 1, 33, 1 << 22, 1 << 22, (4, 9, 1, 64, 1048576, 1074266112), (8, 5, 1, 64, 1048576, 2147483648)),
+    ("Stokes3D-FxUP", 1, 2, 1 << 14, 1 << 23, (2, 1, 2, 64, 2048, 33554432), (2, 1, 2, 8, 131072, 1610612736)),
+    ("Stokes3D-FxUP", 0, 5, 1000, 513, (4, 2, 1, 3, 12, 384000), (8, 1, 1, 4, 12, 393984)),
+    ("Stokes3D-FxUP", 1, 33, 1 << 18, 1 << 18, (4, 9, 1, 8, 8192, 134217728), (8, 5, 1, 24, 24576, 603979776)),
+    ("Stokes3D-FxUP", 0, 4, 1 << 23, 1 << 14, (4, 1, 1, 8, 262144, 2147483648), (4, 1, 1, 64, 4096, 100663296)),
+    ("Stokes3D-FxUP", 1, 11, 300, 300, (4, 3, 1, 2, 4, 38400), (8, 2, 1, 2, 4, 57600)),
+    ("Stokes3D-FxUP", 0, 3, 1 << 14, 1 << 14, (4, 1, 1, 16, 1024, 33554432), (4, 1, 1, 16, 1024, 25165824)),
+    ("Laplace3D-FDxUdU", 0, 4, 1 << 20, 1 << 20, (4, 1, 1, 56, 229376, 1879048192), (4, 1, 1, 64, 262144, 2147483648)),
+    ("Laplace3D-FDxUdU", 1, 11, 1 << 14, 1 << 23, (4, 3, 1, 64, 4096, 67108864), (8, 2, 1, 8, 262144, 2147483648)),
+    ("Laplace3D-FDxUdU", 0, 3, 1000, 513, (4, 1, 1, 3, 12, 384000), (4, 1, 1, 4, 12, 131328)),
+    ("Laplace3D-FDxUdU", 1, 8, 1 << 18, 1 << 18, (4, 2, 1, 8, 8192, 134217728), (8, 1, 1, 24, 24576, 402653184)),
+    ("Laplace3D-FDxUdU", 0, 2, 1 << 23, 1 << 14, (2, 1, 2, 8, 131072, 2147483648), (2, 1, 2, 64, 2048, 33554432)),
+    ("Laplace3D-FDxUdU", 1, 5, 300, 300, (4, 2, 1, 2, 4, 38400), (8, 1, 1, 2, 4, 38400)),
+    ("Helmholtz3D-FxU", 1, 8, 1 << 12, 64, (8, 1, 1, 1, 16, 0), (8, 1, 1, 16, 16, 65536)),
+    ("Helmholtz3D-FxU", 0, 2, 1 << 20, 1 << 20, (2, 1, 2, 32, 65536, 1073741824), (2, 1, 2, 32, 65536, 1073741824)),
+    ("Helmholtz3D-FxU", 1, 5, 1 << 14, 1 << 23, (8, 1, 1, 64, 4096, 67108864), (8, 1, 1, 8, 262144, 2147483648)),
+    ("Helmholtz3D-FxU", 0, 33, 1000, 513, (8, 5, 1, 3, 12, 384000), (8, 5, 1, 4, 12, 262656)),
+    ("Helmholtz3D-FxU", 1, 4, 1 << 18, 1 << 18, (4, 1, 1, 8, 8192, 67108864), (4, 1, 1, 8, 8192, 67108864)),
+    ("Helmholtz3D-FxU", 0, 11, 1 << 23, 1 << 14, (8, 2, 1, 8, 262144, 2147483648), (8, 2, 1, 64, 4096, 134217728)),
+)
+
+
+def test_one_planner_returns_the_plans_of_the_two_it_replaced(monkeypatch):
+    monkeypatch.delenv("SCTL_AMD_TRANSPOSE_WORKSPACE", raising=False)
+    assert len(PLANS_BEFORE_THE_MERGE) >= 60
+    for name, real, nd, Nt, Ns, fwd, trans in PLANS_BEFORE_THE_MERGE:
+        f = sctl_amd.plan_densities(name, real, nd, Nt, Ns)
+        t = sctl_amd.plan_transpose_densities(name, real, nd, Nt, Ns)
+        assert tuple(f[k] for k in ("densities_per_pass", "passes", "trg_per_lane", "src_splits", "workgroups", "workspace_bytes")) == fwd, (name, real, nd, Nt, Ns, f)
+        assert tuple(t[k] for k in ("vectors_per_pass", "passes", "src_per_lane", "splits", "workgroups", "workspace_bytes")) == trans, (name, real, nd, Nt, Ns, t)
+
+
+def test_transpose_workspace_variable_leaves_the_forward_plan_alone(monkeypatch):
+    """The forward bound is a fixed 2 GB: SCTL_AMD_TRANSPOSE_WORKSPACE, which lowers the transposed one, must not reach it through the shared planner."""
+    N = 1 << 22
+    monkeypatch.delenv("SCTL_AMD_TRANSPOSE_WORKSPACE", raising=False)
+    unset = sctl_amd.plan_densities("Stokes3D-FSxU", 0, 8, N, N)
+    t_unset = sctl_amd.plan_transpose_densities("Stokes3D-FSxU", 0, 8, N, N)
+    for v in ("1", str(1 << 20)):
+        monkeypatch.setenv("SCTL_AMD_TRANSPOSE_WORKSPACE", v)
+        assert sctl_amd.plan_densities("Stokes3D-FSxU", 0, 8, N, N) == unset, v
+        assert sctl_amd.plan_transpose_densities("Stokes3D-FSxU", 0, 8, N, N) != t_unset, v   # (the variable is read: it does lower the transposed bound)
+
+
 def _unit_asm(tmp_path, unit):
     flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], capture_output=True, text=True, check=True).stdout.split()
     extra = subprocess.run(["make", "-s", "-C", CSRC, "print-unit-flags", "UNIT=" + unit], capture_output=True, text=True, check=True).stdout.split()

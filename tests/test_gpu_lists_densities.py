@@ -1,4 +1,4 @@
-"""Several densities over the P2P lists in one launch (sctl_amd_lists_eval_densities_*, lists_multi_kernel.hpp) on the GPU: every kernel through
+"""Several densities over the P2P lists in one launch (sctl_amd_lists_eval_densities_*, sctl_amd/csrc/lists_rows_kernel.hpp) on the GPU: every kernel through
 every shape of a work item at every pass width against the CPU oracle's per-list loop and the single-density entry, the reference's goldens
 (tests/golden/p2p_lists.npz), accumulate / nd == 1 / untouched targets / run-to-run / counters / one-shot / side-stream semantics, the accuracy
 ladder, the plugin fallback and the C++ host surface."""

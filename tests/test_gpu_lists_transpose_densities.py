@@ -1,5 +1,5 @@
 """Several weight vectors through the transposed list sum, G[m] += sum over the lists of A_l^T W[m] (sctl_amd_lists_eval_transpose_densities_*,
-sctl_amd/csrc/lists_multi_transpose_kernel.hpp) on the GPU.
+sctl_amd/csrc/lists_rows_kernel.hpp) on the GPU.
 
 Expected value throughout: per list the KernelMatrix block of (target range, source range) from sctl_amd_kernel_matrix_batch_host at full precision —
 the matrix the existing suite pins against the reference, which zeroes coincident pairs —, applied once to all nd rows of W in numpy long double and

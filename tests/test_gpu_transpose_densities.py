@@ -1,4 +1,4 @@
-"""Several weight vectors through the transposed kernel sum, G[m] += A^T W[m] (sctl_amd_eval_transpose_densities_*, sctl_amd/csrc/multi_transpose_kernel.hpp),
+"""Several weight vectors through the transposed kernel sum, G[m] += A^T W[m] (sctl_amd_eval_transpose_densities_*, sctl_amd/csrc/rows_kernel.hpp),
 on the GPU.
 
 Expected value of row m: M . w_m in numpy long double, M from sctl_amd_kernel_matrix_host at full precision, the inputs fp32-representable doubles as in
