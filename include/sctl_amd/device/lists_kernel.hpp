@@ -19,6 +19,7 @@
 //     work item, its targets, the latency of the first sources) is spread over eight boxes instead of one: a leaf of ~8 points went from 4.9 % to
 //     [see DESIGN.md §4.6] of the fp64 peak.
 #pragma once
+#include "dir.hpp"
 #include "eval_kernel.hpp"
 
 namespace sctl_amd {
@@ -64,18 +65,21 @@ template <class R> struct ListArgs {
   const uint32_t* flat;        // their source sequences: indices into xs / xn / f
 };
 
-// One work item with T targets per lane.  Each LDS tile is first evaluated WITHOUT the r = 0 mask into per-tile sums; a coincident
+// One work item with T OWNERS per lane, for both directions: `Dir` (dir.hpp) is DirFwd for lists_kernel — the owners are targets, the sources stream — and
+// DirTrans for lists_transpose_kernel (lists_transpose_kernel.hpp), whose owners are sources with their normals while the targets stream with their weights;
+// A is ListArgs<R> or ListTArgs<R>.  Each LDS tile is first evaluated WITHOUT the r = 0 mask into per-tile sums; a coincident
 // pair (a box acting on itself: 1 of its ~27 lists) poisons them with inf/NaN, which one compare per tile detects, and the wave
 // re-runs that tile masked — the same speculation as eval_kernel.hpp, worth ~9 % on the Laplace kernel.
 //
-// SPLIT (T = 1, at most 32 targets): the wave would idle most of its lanes, so it is cut into 64/P REPLICAS of P lanes (P = the
-// power of two >= the target count, at least 8): every replica holds all the targets and takes every (64/P)-th source of a tile; the
+// SPLIT (T = 1, at most 32 owners): the wave would idle most of its lanes, so it is cut into 64/P REPLICAS of P lanes (P = the
+// power of two >= the owner count, at least 8): every replica holds all the owners and takes every (64/P)-th point of a tile; the
 // replicas' sums are added with a butterfly of lane shuffles at the end (a fixed order: still deterministic).  An 8-point leaf then
-// costs an eighth of a wave pass per source instead of a whole one.
-template <class Ker, class R, int MODE, int T, bool SPLIT, class KC, class V>
-__device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem& it, V* tile, const KC& K) {
-  static_assert(!SPLIT || T == 1, "replicas are for small one-target-per-lane items");
-  constexpr int K0 = Ker::K0, K1 = Ker::K1, ND = Ker::ND, NREC = Ker::NREC;
+// costs an eighth of a wave pass per streamed point instead of a whole one.
+template <class Dir, class Ker, class R, int MODE, int T, bool SPLIT, class A, class KC, class V>
+__device__ __forceinline__ void lists_item(const A& a, const ListItem& it, V* tile, const KC& K) {
+  static_assert(!SPLIT || T == 1, "replicas are for small one-owner-per-lane items");
+  constexpr int KIN = Dir::template KIN<Ker>, KOUT = Dir::template KOUT<Ker>, ND = Ker::ND, NREC = Dir::template NREC<Ker>;
+  constexpr int OWN_N = Dir::template OWN_N<Ker>, STR_N = Dir::template STR_N<Ker>, NN = OWN_N ? OWN_N : 1;
   constexpr int VN = VecOf<R>::N;
   constexpr int NV = (NREC + VN - 1) / VN;
   constexpr int NRECP = NV * VN;
@@ -86,25 +90,27 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
   if (SPLIT) { P = 8; while (P < it.nt) P <<= 1; }
   const int nrep = kListWave / P, rep = lane / P;
 
-  R xt[T][3], acc[T][K1];
+  R xo[T][3], no[T][NN], acc[T][KOUT];     // (no: a dummy where the owner holds no normal; the forward pair ignores it)
 #pragma unroll
   for (int j = 0; j < T; j++) {
-    int tl = SPLIT ? (lane & (P - 1)) : (j * kListWave + lane);
-    if (tl >= it.nt) tl = it.nt - 1;      // idle lanes repeat the last target; never stored
-    const int64_t t = it.t0 + tl;
+    int ol = SPLIT ? (lane & (P - 1)) : (j * kListWave + lane);
+    if (ol >= it.nt) ol = it.nt - 1;      // idle lanes repeat the last owner; never stored
+    const int64_t oi = it.t0 + ol;
 #pragma unroll
-    for (int k = 0; k < 3; k++) xt[j][k] = a.xt[t * 3 + k];
+    for (int k = 0; k < 3; k++) xo[j][k] = Dir::own_x(a)[oi * 3 + k];
 #pragma unroll
-    for (int k = 0; k < K1; k++) acc[j][k] = 0;
+    for (int k = 0; k < NN; k++) no[j][k] = OWN_N ? Dir::own_n(a)[oi * ND + k] : R(0);
+#pragma unroll
+    for (int k = 0; k < KOUT; k++) acc[j][k] = 0;
   }
 
-  // cursor into the concatenated source sequence (wave-uniform): range r, offset o inside it
+  // cursor into the concatenated streamed sequence (wave-uniform): range r, offset o inside it
   int r = 0;
   int64_t o = 0;
-  R sx[3] = {0, 0, 0}, sn[3] = {0, 0, 0}, sf[K0];
+  R sx[3] = {0, 0, 0}, sn[3] = {0, 0, 0}, sr[KIN];
 #pragma unroll
-  for (int k = 0; k < K0; k++) sf[k] = 0;
-  // fetch the next (up to) 64 sources of the sequence into registers, lane i the i-th of them; returns how many
+  for (int k = 0; k < KIN; k++) sr[k] = 0;
+  // fetch the next (up to) 64 points of the sequence into registers, lane i the i-th of them; returns how many
   auto fetch = [&]() -> int {
     int fill = 0;
     int64_t mine = -1;
@@ -118,11 +124,11 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
     }
     if (mine >= 0) {
 #pragma unroll
-      for (int k = 0; k < 3; k++) sx[k] = a.xs[mine * 3 + k];
+      for (int k = 0; k < 3; k++) sx[k] = Dir::str_x(a)[mine * 3 + k];
 #pragma unroll
-      for (int k = 0; k < ND; k++) sn[k] = a.xn[mine * ND + k];
+      for (int k = 0; k < STR_N; k++) sn[k] = Dir::str_n(a)[mine * STR_N + k];
 #pragma unroll
-      for (int k = 0; k < K0; k++) sf[k] = a.f[mine * K0 + k];
+      for (int k = 0; k < KIN; k++) sr[k] = Dir::in(a)[mine * KIN + k];
     }
     return fill;
   };
@@ -134,7 +140,7 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
     __syncthreads();   // previous tile fully consumed
     if (lane < ns) {
       R rec[NRECP] = {};
-      pack_record<Ker, R, MODE>(rec, sx, sn, sf);
+      Dir::template pack<Ker, R, MODE>(rec, sx, sn, sr);
 #pragma unroll
       for (int v = 0; v < NV; v++) {
         V w;
@@ -147,7 +153,7 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
     ns = fetch();      // loads for the next tile are in flight during this tile's arithmetic
     __syncthreads();
 
-    R tacc[T][K1];
+    R tacc[T][KOUT];
     auto run_tile_v = [&](auto masked_tag, auto variant_tag) {
       constexpr bool MASKED = decltype(masked_tag)::value;
       constexpr int VARIANT = decltype(variant_tag)::value;
@@ -155,8 +161,8 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
 #pragma unroll
       for (int j = 0; j < T; j++)
 #pragma unroll
-        for (int k = 0; k < K1; k++) tacc[j][k] = 0;
-      auto one_source = [&](int s) {
+        for (int k = 0; k < KOUT; k++) tacc[j][k] = 0;
+      auto one_point = [&](int s) {
         R rec[NRECP];
 #pragma unroll
         for (int v = 0; v < NV; v++) {
@@ -165,23 +171,19 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
           for (int e = 0; e < VN; e++) rec[v * VN + e] = w[e];
         }
 #pragma unroll
-        for (int j = 0; j < T; j++) {
-          const R d[3] = {xt[j][0] - rec[0], xt[j][1] - rec[1], xt[j][2] - rec[2]};
-          if constexpr (KC::HAS_VARIANT) Ker::template pair<R, MODE, MASKED, VARIANT>(tacc[j], d, rec, a.ctx, K);
-          else Ker::template pair<R, MODE, MASKED>(tacc[j], d, rec, a.ctx, K);
-        }
+        for (int j = 0; j < T; j++) Dir::template pair<Ker, R, MODE, MASKED, VARIANT>(tacc[j], xo[j], no[j], rec, a.ctx, K);
       };
-      if (SPLIT) {                         // replica `rep` takes sources rep, rep + nrep, ... of the tile
+      if (SPLIT) {                         // replica `rep` takes points rep, rep + nrep, ... of the tile
         const int cnt = (ns_cur + nrep - 1) / nrep;   // wave-uniform trip count; the tail of a short tile is predicated
         for (int i = 0; i < cnt; i++) {
           const int s = i * nrep + rep;
-          if (s < ns_cur) one_source(s);
+          if (s < ns_cur) one_point(s);
         }
       } else if (ns_cur == kListTile) {
-#pragma unroll UnrollOf<T, Ker::K1>::value
-        for (int s = 0; s < kListTile; s++) one_source(s);
+#pragma unroll UnrollOf<T, KOUT>::value
+        for (int s = 0; s < kListTile; s++) one_point(s);
       } else {
-        for (int s = 0; s < ns_cur; s++) one_source(s);
+        for (int s = 0; s < ns_cur; s++) one_point(s);
       }
     };
     auto run_tile = [&](auto masked_tag) {   // a launch-uniform special case of the kernel (Helmholtz: real wavenumber) has its own loop
@@ -200,7 +202,7 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
 #pragma unroll
       for (int j = 0; j < T; j++)
 #pragma unroll
-        for (int k = 0; k < K1; k++) bad |= !(fabs_(tacc[j][k]) <= max_finite<R>());
+        for (int k = 0; k < KOUT; k++) bad |= !(fabs_(tacc[j][k]) <= max_finite<R>());
       repaired = __any(bad);                 // wave-uniform
       if (repaired && (++repairs) * 4 > tiles + 4) always_masked = true;   // mostly coincident points (tiny boxes): stop speculating
     }
@@ -208,110 +210,113 @@ __device__ __forceinline__ void lists_item(const ListArgs<R>& a, const ListItem&
 #pragma unroll
     for (int j = 0; j < T; j++)
 #pragma unroll
-      for (int k = 0; k < K1; k++) acc[j][k] += tacc[j][k];
+      for (int k = 0; k < KOUT; k++) acc[j][k] += tacc[j][k];
   }
 
-  if (SPLIT) {                             // add the replicas' sums: lanes l, l ^ P, l ^ 2P, ... hold the same target
+  if (SPLIT) {                             // add the replicas' sums: lanes l, l ^ P, l ^ 2P, ... hold the same owner
     for (int off = P; off < kListWave; off <<= 1)
 #pragma unroll
-      for (int k = 0; k < K1; k++) acc[0][k] += __shfl_xor(acc[0][k], off);
+      for (int k = 0; k < KOUT; k++) acc[0][k] += __shfl_xor(acc[0][k], off);
   }
 #pragma unroll
   for (int j = 0; j < T; j++) {
-    const int tl = SPLIT ? (lane & (P - 1)) : (j * kListWave + lane);
-    finish_acc<Ker, R, MODE>(acc[j]);
-    if (tl < it.nt && (!SPLIT || rep == 0)) {
-      const int64_t t = it.t0 + tl;
+    const int ol = SPLIT ? (lane & (P - 1)) : (j * kListWave + lane);
+    Dir::template finish<Ker, R, MODE>(acc[j]);
+    if (ol < it.nt && (!SPLIT || rep == 0)) {
+      const int64_t oi = it.t0 + ol;
 #pragma unroll
-      for (int k = 0; k < K1; k++) a.v_trg[t * K1 + k] += acc[j][k] * a.scale;   // generic-kernel.txx:184
+      for (int k = 0; k < KOUT; k++) Dir::out(a)[oi * KOUT + k] += acc[j][k] * a.scale;   // generic-kernel.txx:184
     }
   }
 }
 
-// One PACKED work item: up to 64 / P small target ranges, P lanes x T targets per lane each.  Group g = lane / P walks its own source sequence P sources at a
-// time: lane i of the group fetches the (k P + i)-th source, packs it into the group's slice of the LDS tile (slices one 16-byte word apart from a multiple of
-// 32 banks: the groups' reads — one address per group — do not collide), and every lane of the group evaluates its T targets against the slice.  The next step's
-// sources are in flight meanwhile.  Sums are kept per target in list order (per-step partial sums, added in step order): deterministic.
+// One PACKED work item: up to 64 / P small owner ranges, P lanes x T owners per lane each.  Group g = lane / P walks its own streamed sequence P points at a
+// time: lane i of the group fetches the (k P + i)-th point, packs it into the group's slice of the LDS tile (slices one 16-byte word apart from a multiple of
+// 32 banks: the groups' reads — one address per group — do not collide), and every lane of the group evaluates its T owners against the slice.  The next step's
+// points are in flight meanwhile.  Sums are kept per owner in list order (per-step partial sums, added in step order): deterministic.
 // A step runs without the r = 0 mask and is repaired when a coincident pair shows up, as in lists_item — except that a step KNOWN to hold coincident pairs is run
-// masked at once: when the caller's sources ARE its targets (launch-uniform: one array) a lane sees that the source it fetched is one of its group's own
-// targets.  With eight boxes per wave some group is at its own points in a third of the steps; evaluating those twice would cost more than the whole mask.
-template <class Ker, class R, int MODE, int P, int T, int SPL, class KC, class V>
-__device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const ListItem& it, V* tile, const KC& K) {
-  constexpr int K0 = Ker::K0, K1 = Ker::K1, ND = Ker::ND, NREC = Ker::NREC;
+// masked at once: when the caller's sources ARE its targets (launch-uniform: one array) a lane sees that the point it fetched is one of its group's own
+// owners.  With eight boxes per wave some group is at its own points in a third of the steps; evaluating those twice would cost more than the whole mask.
+template <class Dir, class Ker, class R, int MODE, int P, int T, int SPL, class A, class KC, class V>
+__device__ __forceinline__ void lists_packed_item(const A& a, const ListItem& it, V* tile, const KC& K) {
+  constexpr int KIN = Dir::template KIN<Ker>, KOUT = Dir::template KOUT<Ker>, ND = Ker::ND, NREC = Dir::template NREC<Ker>;
+  constexpr int OWN_N = Dir::template OWN_N<Ker>, STR_N = Dir::template STR_N<Ker>, NN = OWN_N ? OWN_N : 1;
   constexpr int VN = VecOf<R>::N;
   constexpr int NV = (NREC + VN - 1) / VN;
   constexpr int NRECP = NV * VN;
-  constexpr int G = kListWave / P, S = P * SPL, SLICE = S * NV + 1;   // S sources per group and step (SPL per lane); 16-byte words per group slice (+ 1: bank spread)
+  constexpr int G = kListWave / P, S = P * SPL, SLICE = S * NV + 1;   // S points per group and step (SPL per lane); 16-byte words per group slice (+ 1: bank spread)
   static_assert(G * SLICE <= kPackedTileWords(NV), "the packed slices fit the list kernel's LDS tile");
   const int lane = threadIdx.x, g = lane / P, i = lane % P;
   const bool live = g < it.nt;                              // (it.nt = groups of this item)
   const PackedGroup pg = a.groups[it.t0 + (live ? g : 0)];
-  const int nsrc = live ? pg.nsrc : 0;
+  const int nstr = live ? pg.nsrc : 0;                      // streamed points of the group
   const bool self = (const void*)a.xs == (const void*)a.xt;
 
-  R xt[T][3], acc[T][K1];
+  R xo[T][3], no[T][NN], acc[T][KOUT];
 #pragma unroll
   for (int j = 0; j < T; j++) {
-    int tl = j * P + i;
-    if (tl >= pg.nt) tl = pg.nt - 1;                        // idle slots repeat the last target; never stored
-    const int64_t t = pg.t0 + tl;
+    int ol = j * P + i;
+    if (ol >= pg.nt) ol = pg.nt - 1;                        // idle slots repeat the last owner; never stored
+    const int64_t oi = pg.t0 + ol;
 #pragma unroll
-    for (int k = 0; k < 3; k++) xt[j][k] = a.xt[t * 3 + k];
+    for (int k = 0; k < 3; k++) xo[j][k] = Dir::own_x(a)[oi * 3 + k];
 #pragma unroll
-    for (int k = 0; k < K1; k++) acc[j][k] = 0;
+    for (int k = 0; k < NN; k++) no[j][k] = OWN_N ? Dir::own_n(a)[oi * ND + k] : R(0);
+#pragma unroll
+    for (int k = 0; k < KOUT; k++) acc[j][k] = 0;
   }
-  int nmax = nsrc;                                          // the longest sequence of the wave decides the trip count
+  int nmax = nstr;                                          // the longest sequence of the wave decides the trip count
   for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(nmax, o); nmax = (w > nmax) ? w : nmax; }
   nmax = __builtin_amdgcn_readfirstlane(nmax);
   const int nsteps = (nmax + S - 1) / S;
 
-  R sx[SPL][3], sn[SPL][3], sf[SPL][K0];
+  R sx[SPL][3], sn[SPL][3], sr[SPL][KIN];
 #pragma unroll
   for (int u = 0; u < SPL; u++) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { sx[u][k] = 0; sn[u][k] = 0; }
 #pragma unroll
-    for (int k = 0; k < K0; k++) sf[u][k] = 0;
+    for (int k = 0; k < KIN; k++) sr[u][k] = 0;
   }
-  // The sources of a step are fetched one step ahead, their INDICES two steps ahead: index -> coordinates is a chain of two memory latencies, and a step
-  // is short.  Lane i of a group holds sources u P + i, u < SPL, of the step's S.  idx_next: its sources of the step after the one being gathered (kNone: none).
-  // Everything here is 32-bit: the plan packs small ranges only while every source array is under 4 GB (lists.hip), so a source's byte offset fits an unsigned
+  // The points of a step are fetched one step ahead, their INDICES two steps ahead: index -> coordinates is a chain of two memory latencies, and a step
+  // is short.  Lane i of a group holds points u P + i, u < SPL, of the step's S.  idx_next: its points of the step after the one being gathered (kNone: none).
+  // Everything here is 32-bit: the plan packs small ranges only while every streamed array is under 4 GB (lists.hip), so a point's byte offset fits an unsigned
   // 32-bit register and its loads take the (scalar base, 32-bit lane offset) form — the 64-bit per-lane address arithmetic was a third of a step's bookkeeping.
   constexpr uint32_t kNone = 0xffffffffu;
   const uint32_t own_lo = (uint32_t)pg.t0, own_n = self ? (uint32_t)pg.nt : 0u;   // (own points exist only when the sources ARE the targets)
   const uint32_t* const flat_g = a.flat + pg.flat_off;
-  bool own = false;    // a source this lane holds for the coming step is one of its group's targets
+  bool own = false;    // a point this lane holds for the coming step is one of its group's owners
   uint32_t idx_next[SPL];
   auto load_idx = [&](int step) {
 #pragma unroll
     for (int u = 0; u < SPL; u++) {
       const int q = step * S + u * P + i;
-      idx_next[u] = (q < nsrc) ? flat_g[q] : kNone;
+      idx_next[u] = (q < nstr) ? flat_g[q] : kNone;
     }
   };
   if (nsteps > 0) load_idx(0);
   auto at = [](const R* base, uint32_t byte_off) -> const R* { return (const R*)((const char*)base + byte_off); };
   auto fetch = [&](int step) {
-    uint32_t src[SPL];
+    uint32_t str[SPL];
 #pragma unroll
-    for (int u = 0; u < SPL; u++) src[u] = idx_next[u];
+    for (int u = 0; u < SPL; u++) str[u] = idx_next[u];
     if (step + 1 < nsteps) load_idx(step + 1);
     own = false;
 #pragma unroll
     for (int u = 0; u < SPL; u++) {
-      if (src[u] != kNone) {
-        own = own || (src[u] - own_lo < own_n);
-        const R* const px = at(a.xs, src[u] * (uint32_t)(3 * sizeof(R)));
+      if (str[u] != kNone) {
+        own = own || (str[u] - own_lo < own_n);
+        const R* const px = at(Dir::str_x(a), str[u] * (uint32_t)(3 * sizeof(R)));
 #pragma unroll
         for (int k = 0; k < 3; k++) sx[u][k] = px[k];
-        if (ND > 0) {
-          const R* const pn = at(a.xn, src[u] * (uint32_t)(ND * sizeof(R)));
+        if (STR_N > 0) {
+          const R* const pn = at(Dir::str_n(a), str[u] * (uint32_t)(STR_N * sizeof(R)));
 #pragma unroll
-          for (int k = 0; k < ND; k++) sn[u][k] = pn[k];
+          for (int k = 0; k < STR_N; k++) sn[u][k] = pn[k];
         }
-        const R* const pf = at(a.f, src[u] * (uint32_t)(K0 * sizeof(R)));
+        const R* const pi = at(Dir::in(a), str[u] * (uint32_t)(KIN * sizeof(R)));
 #pragma unroll
-        for (int k = 0; k < K0; k++) sf[u][k] = pf[k];
+        for (int k = 0; k < KIN; k++) sr[u][k] = pi[k];
       }
     }
   };
@@ -319,13 +324,13 @@ __device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const Li
   if (nsteps > 0) fetch(0);
   for (int step = 0; step < nsteps; step++) {
     __syncthreads();   // previous slices fully consumed
-    const int cnt = nsrc - step * S;                        // sources of this group in this step: >= S (full), 1 .. S - 1 (its last), <= 0 (done)
-    const bool known_coincident = __any(own);               // (of the step being staged now: `own` belongs to the sources fetched for it)
+    const int cnt = nstr - step * S;                        // points of this group in this step: >= S (full), 1 .. S - 1 (its last), <= 0 (done)
+    const bool known_coincident = __any(own);               // (of the step being staged now: `own` belongs to the points fetched for it)
 #pragma unroll
     for (int u = 0; u < SPL; u++) {
       if (u * P + i < cnt) {
         R rec[NRECP] = {};
-        pack_record<Ker, R, MODE>(rec, sx[u], sn[u], sf[u]);
+        Dir::template pack<Ker, R, MODE>(rec, sx[u], sn[u], sr[u]);
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           V w;
@@ -338,7 +343,7 @@ __device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const Li
     if (step + 1 < nsteps) fetch(step + 1);
     __syncthreads();
 
-    R tacc[T][K1];
+    R tacc[T][KOUT];
     const bool full = __all(cnt >= S);                      // wave-uniform: every group has a whole slice (all steps but the groups' last ones)
     auto run_step_v = [&](auto masked_tag, auto variant_tag) {
       constexpr bool MASKED = decltype(masked_tag)::value;
@@ -347,8 +352,8 @@ __device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const Li
 #pragma unroll
       for (int j = 0; j < T; j++)
 #pragma unroll
-        for (int k = 0; k < K1; k++) tacc[j][k] = 0;
-      auto one_source = [&](int s) {
+        for (int k = 0; k < KOUT; k++) tacc[j][k] = 0;
+      auto one_point = [&](int s) {
         R rec[NRECP];
 #pragma unroll
         for (int v = 0; v < NV; v++) {
@@ -357,21 +362,17 @@ __device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const Li
           for (int e = 0; e < VN; e++) rec[v * VN + e] = w[e];
         }
 #pragma unroll
-        for (int j = 0; j < T; j++) {
-          const R d[3] = {xt[j][0] - rec[0], xt[j][1] - rec[1], xt[j][2] - rec[2]};
-          if constexpr (KC::HAS_VARIANT) Ker::template pair<R, MODE, MASKED, VARIANT>(tacc[j], d, rec, a.ctx, K);
-          else Ker::template pair<R, MODE, MASKED>(tacc[j], d, rec, a.ctx, K);
-        }
+        for (int j = 0; j < T; j++) Dir::template pair<Ker, R, MODE, MASKED, VARIANT>(tacc[j], xo[j], no[j], rec, a.ctx, K);
       };
       if (full) {
-#pragma unroll UnrollOf<T, Ker::K1>::value
-        for (int s = 0; s < S; s++) one_source(s);
-      } else {                                              // a group's last step: its remaining sources, the other groups' lanes idle
+#pragma unroll UnrollOf<T, KOUT>::value
+        for (int s = 0; s < S; s++) one_point(s);
+      } else {                                              // a group's last step: its remaining points, the other groups' lanes idle
         int cmax = cnt;
         for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(cmax, o); cmax = (w > cmax) ? w : cmax; }
         cmax = __builtin_amdgcn_readfirstlane(cmax < S ? cmax : S);
         for (int s = 0; s < cmax; s++)
-          if (s < cnt) one_source(s);
+          if (s < cnt) one_point(s);
       }
     };
     auto run_step = [&](auto masked_tag) {
@@ -389,29 +390,32 @@ __device__ __forceinline__ void lists_packed_item(const ListArgs<R>& a, const Li
 #pragma unroll
       for (int j = 0; j < T; j++)
 #pragma unroll
-        for (int k = 0; k < K1; k++) bad |= !(fabs_(tacc[j][k]) <= max_finite<R>());
+        for (int k = 0; k < KOUT; k++) bad |= !(fabs_(tacc[j][k]) <= max_finite<R>());
       repaired = __any(bad);
     }
     if (repaired) run_step(std::true_type());
 #pragma unroll
     for (int j = 0; j < T; j++)
 #pragma unroll
-      for (int k = 0; k < K1; k++) acc[j][k] += tacc[j][k];
+      for (int k = 0; k < KOUT; k++) acc[j][k] += tacc[j][k];
   }
 #pragma unroll
   for (int j = 0; j < T; j++) {
-    const int tl = j * P + i;
-    finish_acc<Ker, R, MODE>(acc[j]);
-    if (live && tl < pg.nt) {
-      const int64_t t = pg.t0 + tl;
+    const int ol = j * P + i;
+    Dir::template finish<Ker, R, MODE>(acc[j]);
+    if (live && ol < pg.nt) {
+      const int64_t oi = pg.t0 + ol;
 #pragma unroll
-      for (int k = 0; k < K1; k++) a.v_trg[t * K1 + k] += acc[j][k] * a.scale;   // generic-kernel.txx:184
+      for (int k = 0; k < KOUT; k++) Dir::out(a)[oi * KOUT + k] += acc[j][k] * a.scale;   // generic-kernel.txx:184
     }
   }
 }
 
-// An item with more than 64 targets runs two targets per lane (half the LDS reads per pair), one with 33..64 a single target per
-// lane (no idle second slot), a smaller one replicas of 8..32 lanes (lists_item, SPLIT); lists.hip cuts the target ranges accordingly.
+// An item with more than 64 owners runs two owners per lane (half the LDS reads per pair), one with 33..64 a single owner per lane (no idle second slot), a
+// smaller one replicas of 8..32 lanes (lists_item, SPLIT); the four packed classes are 8 x 1, 8 x 2, 16 x 2 and 32 x 2 owners.  lists.hip cuts the owner ranges
+// accordingly.  The LDS declarations, the item lookup and this dispatch are written in the kernel, and again in lists_transpose_kernel with NREC_T, ListTArgs and
+// DirTrans: moved into a function of their own they change the order in which the compiler simplifies the walkers, and the kernels come out with 1 - 3 VGPRs
+// more (profiles/r19_single_row_one_body.txt).
 template <class Ker, class R, int MODE>
 __global__ void __launch_bounds__(kListWave) lists_kernel(const ListArgs<R> a) {
   using V = typename VecOf<R>::type;
@@ -428,17 +432,17 @@ __global__ void __launch_bounds__(kListWave) lists_kernel(const ListArgs<R> a) {
   const int xcd = blockIdx.x % 8, j = blockIdx.x / 8;
   if (j >= a.xcd_first[xcd + 1] - a.xcd_first[xcd]) return;
   const ListItem it = a.items[a.xcd_first[xcd] + j];
-  if (it.nranges < 0) {      // packed small target ranges
+  if (it.nranges < 0) {      // packed small owner ranges
     const int cls = -1 - it.nranges;
-    if (cls == 0) lists_packed_item<Ker, R, MODE, 8, 1, 2>(a, it, tile, K);
-    else if (cls == 1) lists_packed_item<Ker, R, MODE, 8, 2, 2>(a, it, tile, K);
-    else if (cls == 2) lists_packed_item<Ker, R, MODE, 16, 2, 2>(a, it, tile, K);
-    else lists_packed_item<Ker, R, MODE, 32, 2, 1>(a, it, tile, K);
+    if (cls == 0) lists_packed_item<DirFwd, Ker, R, MODE, 8, 1, 2>(a, it, tile, K);
+    else if (cls == 1) lists_packed_item<DirFwd, Ker, R, MODE, 8, 2, 2>(a, it, tile, K);
+    else if (cls == 2) lists_packed_item<DirFwd, Ker, R, MODE, 16, 2, 2>(a, it, tile, K);
+    else lists_packed_item<DirFwd, Ker, R, MODE, 32, 2, 1>(a, it, tile, K);
     return;
   }
-  if (it.nt > kListWave) lists_item<Ker, R, MODE, 2, false>(a, it, tile, K);
-  else if (it.nt > kListWave / 2) lists_item<Ker, R, MODE, 1, false>(a, it, tile, K);
-  else lists_item<Ker, R, MODE, 1, true>(a, it, tile, K);
+  if (it.nt > kListWave) lists_item<DirFwd, Ker, R, MODE, 2, false>(a, it, tile, K);
+  else if (it.nt > kListWave / 2) lists_item<DirFwd, Ker, R, MODE, 1, false>(a, it, tile, K);
+  else lists_item<DirFwd, Ker, R, MODE, 1, true>(a, it, tile, K);
 }
 
 }  // namespace sctl_amd

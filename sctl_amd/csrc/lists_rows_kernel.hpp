@@ -19,7 +19,7 @@
 // fp32 runs this exact vector-pipe pair at every accuracy, as eval_multi_kernel and every transposed kernel do.
 //
 // The two directions differ only in the policy `Dir` (ListFwd, ListTrans below): which of K0 / K1 is the output width, the record, who carries the normal, the
-// sign of d (rows_dir.hpp), and the names of the fields of ListArgs / ListTArgs.  Everything else — the walker, the form, the dispatch, the launch table — exists once.
+// sign of d (rows_dir.hpp), and the names of the fields of ListArgs / ListTArgs (device/dir.hpp).  Everything else — the walker, the form, the dispatch, the launch table — exists once.
 #pragma once
 #include <sctl_amd/device/launch.hpp>
 #include <sctl_amd/device/lists_kernel.hpp>
@@ -38,29 +38,15 @@ template <class L> struct ListRowsArgs {
 template <class R> using ListMultiArgs = ListRowsArgs<ListArgs<R>>;
 template <class R> using ListMultiTArgs = ListRowsArgs<ListTArgs<R>>;
 
-// The direction-only half of the policy (widths, record, pack, pair, finish) is RowsFwd / RowsTrans of rows_dir.hpp, shared with the all-pairs kernels; what is
-// added here is about ListArgs / ListTArgs.  Forward: the owners are the targets.
-struct ListFwd : RowsFwd {
+// Everything about the direction is RowsFwd / RowsTrans of rows_dir.hpp, shared with the all-pairs kernels: the M-row record, pack and pair, and — inherited from
+// the single-row policies of device/dir.hpp — the widths, the finish hook and the fields of ListArgs / ListTArgs.  Added here: the side and the argument type.
+struct ListFwd : RowsFwd {            // the owners are the targets
   static constexpr int SIDE = 0;      // of sctl_amd_lists::side
   template <class R> using Args = ListMultiArgs<R>;
-  template <class R> static __device__ __forceinline__ const R* own_x(const ListArgs<R>& l) { return l.xt; }
-  template <class R> static __device__ __forceinline__ const R* own_n(const ListArgs<R>&) { return nullptr; }
-  template <class R> static __device__ __forceinline__ const R* str_x(const ListArgs<R>& l) { return l.xs; }
-  template <class R> static __device__ __forceinline__ const R* str_n(const ListArgs<R>& l) { return l.xn; }
-  template <class R> static __device__ __forceinline__ const R* in(const ListArgs<R>& l) { return l.f; }
-  template <class R> static __device__ __forceinline__ R* out(const ListArgs<R>& l) { return l.v_trg; }
 };
-
-// Transposed: the owners are the sources, each with its normal.
-struct ListTrans : RowsTrans {
+struct ListTrans : RowsTrans {        // the owners are the sources, each with its normal
   static constexpr int SIDE = 1;
   template <class R> using Args = ListMultiTArgs<R>;
-  template <class R> static __device__ __forceinline__ const R* own_x(const ListTArgs<R>& l) { return l.xs; }
-  template <class R> static __device__ __forceinline__ const R* own_n(const ListTArgs<R>& l) { return l.xn; }
-  template <class R> static __device__ __forceinline__ const R* str_x(const ListTArgs<R>& l) { return l.xt; }
-  template <class R> static __device__ __forceinline__ const R* str_n(const ListTArgs<R>&) { return nullptr; }
-  template <class R> static __device__ __forceinline__ const R* in(const ListTArgs<R>& l) { return l.w; }
-  template <class R> static __device__ __forceinline__ R* out(const ListTArgs<R>& l) { return l.g_src; }
 };
 
 // A workgroup is ONE wave: two waves per SIMD are eight workgroups per CU, so a form may use an eighth of the CU's 160 KB of LDS.
@@ -85,7 +71,7 @@ template <class Dir, class Ker, class R, int M> struct ListRowsForm {
   static constexpr bool TWO = regs(2, SPL2 ? 2 : 1) <= 252;   // (256 by the estimate spilt: forward Stokes3D_DxU fp64, 4 densities)
 };
 
-// lists_item / lists_t_item of the single-row kernels for M rows.  T owners per lane are held; slot j of the lane is owner (j0 + j) * 64 + lane of the item
+// lists_item of the single-row kernels for M rows.  T owners per lane are held; slot j of the lane is owner (j0 + j) * 64 + lane of the item
 // (j0 = 1: the second half of a 128-owner item run in halves).
 template <class Dir, class Ker, class R, int MODE, int M, int T, bool SPLIT, class A, class KC, class V>
 __device__ __forceinline__ void lists_rows_item(const A& a, const ListItem& it, V* tile, const KC& K, const int j0) {
@@ -266,7 +252,7 @@ __device__ __forceinline__ void lists_rows_item(const A& a, const ListItem& it, 
   }
 }
 
-// lists_packed_item / lists_t_packed_item of the single-row kernels for M rows.  T owners per lane are held; slot j of a lane is owner (j0 + j) * P + i of its
+// lists_packed_item of the single-row kernels for M rows.  T owners per lane are held; slot j of a lane is owner (j0 + j) * P + i of its
 // group (j0 = 1: the second half of a two-owners-per-lane class run in halves; a wave whose groups all fit the first half skips it).
 template <class Dir, class Ker, class R, int MODE, int M, int P, int T, int SPL, class A, class KC, class V>
 __device__ __forceinline__ void lists_rows_packed_item(const A& a, const ListItem& it, V* tile, const KC& K, const int j0) {
