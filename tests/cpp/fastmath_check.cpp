@@ -107,6 +107,87 @@ int main() {
     c_specials = c_specials && !CexpCoeffsK::usable(0.0, 0.0) && !CexpCoeffsK::usable(-7.5, 0.1) && !CexpCoeffsK::usable(1.0, 0.26) && !CexpCoeffsK::usable(1.0, -0.26);
     printf("cexp_rel_err %.3e\ncexp_real_abs_err %.3e\ncexp_specials %d\ntwo_reductions_rel_err %.3e\n", ce, cre, (int)c_specials, two);
   }
+  // The constants a launch really runs: the kernel hands the distance in as the double C r (C = helmholtz_dist_factor(mode): 2 for mode 1,
+  // 0x1.555555p+1 for mode 2, the default) and set_scaled folds C into the reduction step and the polynomial.  Both forms, per C, over the
+  // wavenumbers of tests/test_gpu_helmholtz_pairs.py: the argument is the double x = C r, the truth is taken at x / C in 113-bit arithmetic, the
+  // measure is the modulus of the complex error relative to |e^{ikr}|, of the EXACT product of the factors a form returns (D_m times the node
+  // value, the exponential times sine / cosine: the kernel multiplies them into the amplitude 1/r in its own order, and the roundings of that
+  // belong to the per-pair probes on the device).  C = 1 runs through the same loop (the keys *_c1), so the three columns
+  // are of one measurement.  The one-reduction form also gets distances within one step h of EVERY period boundary m 2 pi / kr, m = 1 .. 255
+  // (m = 255 lies at a phase of 1602, past kCexpMaxPhase but inside the 256 periods the tables hold: the last period factor is read there).
+  {
+    static double ctab[kCexpTableDoubles];
+    const double Cs[3] = {1.0, 2.0, 22369621.0 / 8388608.0};      // the last is 0x1.555555p+1 exactly (C++14 has no hexadecimal literals)
+    const char* tag[3] = {"c1", "c2", "c83"};
+    // (Re k, Im k); kappa = -Im k.  The first six are usable by the one-reduction form, the last five are its refusals
+    const double wkr[11] = {7.5, 7.5, 40.0, 40.0, 900.0, 1e-3, 40.0, -3.0, 0.0, 3.0, 5.0};
+    const double wki[11] = {0.3, 0.0, 10.0, -10.0, 5.0, 2e-4, nextafter(10.0, 11.0), 2.5, 0.7, 60.0, -2.0};
+    bool edges = true;
+    for (int m = 0; m < 11; m++) edges = edges && (CexpCoeffsK::usable(wkr[m], -wki[m]) == (m < 6));
+    edges = edges && CexpCoeffsK::usable(40.0, 10.0) && CexpCoeffsK::usable(40.0, -10.0) && !CexpCoeffsK::usable(40.0, nextafter(10.0, 11.0)) &&
+            !CexpCoeffsK::usable(40.0, -nextafter(10.0, 11.0)) && !CexpCoeffsK::usable(nextafter(40.0, 39.0), 10.0);
+    for (int ic = 0; ic < 3; ic++) {
+      const double Cd = Cs[ic];
+      const __float128 Cq = (__float128)Cd;
+      double one = 0, two = 0, bnd = 0;
+      for (int m = 0; m < 11; m++) {
+        const double kr = wkr[m], kappa = -wki[m];
+        const __float128 krq = (__float128)kr, kapq = (__float128)kappa;
+        TabCoeffsK TK;
+        TK.set_scaled(kr, kappa, T, Cd);
+        // |error| / |e^{ikr}| of the value amp (c + i s) for the argument x = C r
+        auto err_of = [&](double x, __float128 re, __float128 im) {
+          const __float128 r = (__float128)x / Cq, ph = krq * r, mag = expq(kapq * r);
+          const __float128 er = re - mag * cosq(ph), ei = im - mag * sinq(ph);
+          return (double)(sqrtq(er * er + ei * ei) / mag);
+        };
+        auto two_at = [&](double x) {
+          double s2, c2;
+          sincos_tab_k(x, s2, c2, TK, table);
+          const double a2 = exp_tab_k(x, TK, table);
+          return err_of(x, (__float128)a2 * (__float128)c2, (__float128)a2 * (__float128)s2);
+        };
+        double rmax2 = 1e6;
+        if (kr != 0) rmax2 = fmin(rmax2, kSincosTabMaxArg / fabs(kr));
+        if (kappa != 0) rmax2 = fmin(rmax2, 700.0 / fabs(kappa));        // relative accuracy where the result is a normal number
+        for (int i = 0; i < 100000; i++) {
+          const double u = drand48(), x = ((i % 3 == 0) ? u * u * u : u) * rmax2 * Cd;
+          two = fmax(two, two_at(x));
+        }
+        if (m >= 6) continue;
+        CexpCoeffsK CK;
+        CK.set_scaled(kr, kappa, T, Cd);
+        for (int t = 0; t < 5; t++) fill_cexp_tables(ctab, t, 5, kr, kappa, K, T);      // the tables do not depend on C
+        auto one_at = [&](double x) {
+          double re, im, dm;
+          cexp_tab_k(x, re, im, dm, CK, ctab);
+          double e = err_of(x, (__float128)dm * (__float128)re, (__float128)dm * (__float128)im);
+          if (kappa == 0) {
+            cexp_tab_k_real(x, re, im, CK, ctab);
+            e = fmax(e, err_of(x, re, im));
+          }
+          return e;
+        };
+        const double rmax1 = kCexpMaxPhase / kr;
+        for (int i = 0; i < 100000; i++) {
+          const double u = drand48(), x = ((i % 3 == 0) ? u * u * u : u) * rmax1 * Cd;
+          one = fmax(one, one_at(x));
+        }
+        const double period = 6.283185307179586476925 / kr, h = period / kCexpNodes;
+        for (int p = 1; p < kCexpPeriods; p++)
+          for (int i = 0; i < 40; i++) {
+            const double d = (i == 0) ? 0.0 : (i == 1) ? h : (i == 2) ? -h : (drand48() * 2 - 1) * h;
+            bnd = fmax(bnd, one_at((p * period + d) * Cd));
+          }
+        double re, im, dm, s2, c2;
+        cexp_tab_k(0.0, re, im, dm, CK, ctab);
+        sincos_tab_k(0.0, s2, c2, TK, table);
+        edges = edges && re == 1.0 && im == 0.0 && dm == 1.0 && s2 == 0.0 && c2 == 1.0 && exp_tab_k(0.0, TK, table) == 1.0;
+      }
+      printf("cexp_rel_err_%s %.3e\ncexp_boundary_rel_err_%s %.3e\ntwo_reductions_rel_err_%s %.3e\n", tag[ic], one, tag[ic], bnd, tag[ic], two);
+    }
+    printf("scaled_edges %d\n", (int)edges);
+  }
   double s1, c1;
   sincos_tab(0.0, s1, c1, T, table);
   const bool tab_specials = exp_tab(-1e9, T, table) == 0.0 && std::isinf(exp_tab(1e9, T, table)) && exp_tab(0.0, T, table) == 1.0 &&

@@ -25,3 +25,14 @@ def test_fastmath_against_libm(tmp_path):
     # two-reduction form — the product of a 2.5e-16 exponential and a 2.9e-16 sine / cosine — is 4.9e-16 on the same arguments: the new
     # form must not be worse than the one it replaces, and a real wavenumber stays below 3e-16.
     assert v["cexp_rel_err"] < 5e-16 and v["cexp_rel_err"] <= v["two_reductions_rel_err"] and v["cexp_real_abs_err"] < 3e-16 and v["cexp_specials"] == 1
+    # the constants a launch runs: the distance arrives as C r with C = 1, 2 or 0x1.555555p+1 by accuracy mode, and set_scaled folds C into the
+    # reduction step and the polynomial.  Both forms per C over the eleven wavenumbers of tests/test_gpu_helmholtz_pairs.py (six the one-reduction
+    # form accepts, among them the decay ratio of exactly 1/4 with either sign, and its five refusals), truth at (C r) / C in 113 bits; the
+    # one-reduction form also within one step h of every period boundary m = 1 .. 255.  The bar is the one-reduction form's 5e-16 from above.
+    # (No ordering between the two forms is asserted per C: per wavenumber it does not hold.)
+    print(out)
+    for c in ("c1", "c2", "c83"):
+        for key in ("cexp_rel_err_", "cexp_boundary_rel_err_", "two_reductions_rel_err_"):
+            assert v[key + c] < 5e-16, (key + c, v[key + c])
+    # usable(): |Im k| = Re k / 4 exactly is accepted, the next double refused; the values at r = 0 are exact for every C
+    assert v["scaled_edges"] == 1
