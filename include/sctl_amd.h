@@ -507,7 +507,7 @@ int sctl_amd_eval_lists_host(int kernel, int real, int64_t nlists, const int64_t
  * unknown bit, and evaluating a direction the plan was not made for, are SCTL_AMD_ERR_BAD_ARGUMENT; a kernel without a transposed form
  * (a plugin functor without pair_t) gets SCTL_AMD_ERR_UNKNOWN_KERNEL from a create that asks for TRANSPOSE.  The counters grow by the
  * plan's pairs.  _host reuses the handle's stream, staging and device buffers (w_trg has the size of v_trg, g_src that of v_src).
- * Several weight vectors: sctl_amd_lists_eval_transpose_densities_* below.  Not built: geometry gradients and several GPUs over lists. */
+ * Several weight vectors: sctl_amd_lists_eval_transpose_densities_* below; geometry gradients: sctl_amd_lists_eval_grad_*.  Not built: several GPUs over lists. */
 #define SCTL_AMD_LISTS_FORWARD 1
 #define SCTL_AMD_LISTS_TRANSPOSE 2
 int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt,
@@ -522,6 +522,26 @@ int sctl_amd_lists_transpose_info(const sctl_amd_lists* plan, int64_t* pairs, in
 int sctl_amd_eval_lists_transpose_host(int kernel, int real, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
                                        const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                                        const void* w_trg, void* g_src, int digits, const void* ctx, int ctx_bytes, int device);
+
+/* ---- geometry gradients over the lists: the gradients of L = sum over the lists of <w_trg, A_l v_src> with respect to the target coordinates
+ * (g_trg, Nt*3 values), the source coordinates (g_src, Ns*3) and the source normals (g_nrm, Ns*3; kernels with a normal), with the definitions
+ * and signs of sctl_amd_eval_grad_*: d = x_t - x_s, a coincident pair contributes 0, a pair named by several lists counts once per list, every
+ * output is ACCUMULATED into.  A NULL output is not computed: g_trg comes from ONE launch over the plan's FORWARD work list (the targets own the
+ * sums), g_src and g_nrm from ONE launch over its TRANSPOSE work list (the sources own them); a side none of whose outputs is asked for is not
+ * launched.  No atomics, no workspace: results are bit-identical from run to run.  All ten built-in kernels, fp64 and fp32 (the exact
+ * vector-pipe pair), every digits.  Checks, in order: a null handle (SCTL_AMD_ERR_BAD_ARGUMENT); a plugin kernel (SCTL_AMD_ERR_UNKNOWN_KERNEL:
+ * the gradient forms are built for the built-in kernels); g_trg with a plan made without SCTL_AMD_LISTS_FORWARD, g_src or g_nrm with one made
+ * without SCTL_AMD_LISTS_TRANSPOSE, g_nrm for a kernel without a normal (SCTL_AMD_ERR_BAD_ARGUMENT); the context.  The counters grow by the
+ * pairs of each launched side.  _host goes through the handle's stream, staging and device buffers; sources that ARE the targets (one array)
+ * keep one device copy.  The one-shot form plans both directions.  Not built: several rows, plugins, the operator handle, several GPUs. */
+int sctl_amd_lists_eval_grad_device(sctl_amd_lists* plan, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, const void* w_trg,
+                                    void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes, void* stream);
+int sctl_amd_lists_eval_grad_host(sctl_amd_lists* plan, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, const void* w_trg,
+                                  void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes);
+int sctl_amd_eval_lists_grad_host(int kernel, int real, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                  const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
+                                  const void* v_src, const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx,
+                                  int ctx_bytes, int device);
 
 /* Several densities over the lists of one plan (the several-densities text above applies): density-major v_src[nd][Ns*SrcDim] and
  * v_trg[nd][Nt*TrgDim], every row ACCUMULATED into.  The plan does not depend on nd: one handle serves the single-density entries and any

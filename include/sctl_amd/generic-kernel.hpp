@@ -255,6 +255,42 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_lists_transpose_host");
   }
 
+  // EvalGrad over P2P lists (sctl_amd_eval_lists_grad_host; not in the reference): the gradients of L = sum over the lists of <w_trg, A_l v_src> with
+  // EvalGrad's definitions and signs, a pair named by several lists counting once per list.  Both directions are planned: the TARGET ranges of any two
+  // lists must be identical or disjoint, and so must the SOURCE ranges.  A null output is not computed; g_nrm must be null for a kernel without a normal.
+  // Each output follows Eval's rule: the right size is accumulated into, any other is resized and zeroed.
+  template <class Real, Integer digits = -1>
+  void EvalListsGrad(Vector<Real>* g_trg, Vector<Real>* g_src, Vector<Real>* g_nrm, const Vector<Real>& r_trg, const Vector<Real>& r_src,
+                     const Vector<Real>& n_src, const Vector<Real>& v_src, const Vector<Real>& w_trg, const Vector<Long>& trg_off, const Vector<Long>& trg_cnt,
+                     const Vector<Long>& src_off, const Vector<Long>& src_cnt) const {
+    static_assert(sizeof(Long) == sizeof(int64_t), "Long must be 64 bits wide");
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM, nl = trg_off.Dim();
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(v_src.Dim() == Ns * KDIM0);
+    SCTL_AMD_ASSERT(w_trg.Dim() == Nt * KDIM1);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(!g_nrm || N_DIM);
+    SCTL_AMD_ASSERT(trg_cnt.Dim() == nl && src_off.Dim() == nl && src_cnt.Dim() == nl);
+    auto size = [](Vector<Real>* g, Long n) {
+      if (g && g->Dim() != n) {
+        g->ReInit(n);
+        g->SetZero();
+      }
+    };
+    size(g_trg, Nt * DIM);
+    size(g_src, Ns * DIM);
+    size(g_nrm, Ns * DIM);
+    if (!nl) return;
+    RequireSupported();
+    auto i64 = [](const Vector<Long>& v) { return reinterpret_cast<const int64_t*>(&v[0]); };
+    const int rc = sctl_amd_eval_lists_grad_host(DeviceKernelId(), RealTag<Real>::value, nl, i64(trg_off), i64(trg_cnt), i64(src_off), i64(src_cnt), Nt, Ns,
+                                                 r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, v_src.begin(), w_trg.begin(),
+                                                 g_trg ? g_trg->begin() : nullptr, g_src ? g_src->begin() : nullptr, g_nrm ? g_nrm->begin() : nullptr, (int)digits,
+                                                 ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_lists_grad_host");
+  }
+
   // EvalListsTranspose for several weight vectors in one launch per pass (sctl_amd_eval_lists_transpose_densities_host): row m of W (nd x Nt*TrgDim)
   // is a vector of target weights, row m of G (nd x Ns*SrcDim) what EvalListsTranspose gives for it — A^T W for the block EvalListsDensities sent
   // through A.  G follows EvalDensities' rule: the right size is accumulated into, any other is resized and zeroed.  nd == 1 is EvalListsTranspose's

@@ -40,7 +40,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_eval_transpose_densities_device", "sctl_amd_eval_transpose_densities_host", "sctl_amd_eval_transpose_densities_plan",
            "sctl_amd_near_apply_transpose_densities_host", "sctl_amd_near_apply_transpose_densities_device", "sctl_amd_op_eval_transpose_densities",
            "sctl_amd_op_eval_potential_transpose_densities",
-           "sctl_amd_eval_grad_densities_device", "sctl_amd_eval_grad_densities_host", "sctl_amd_eval_grad_densities_plan"]
+           "sctl_amd_eval_grad_densities_device", "sctl_amd_eval_grad_densities_host", "sctl_amd_eval_grad_densities_plan",
+           "sctl_amd_lists_eval_grad_device", "sctl_amd_lists_eval_grad_host", "sctl_amd_eval_lists_grad_host"]
 
 
 class SctlAmdError(RuntimeError):
@@ -159,6 +160,9 @@ def lib():
     L.sctl_amd_eval_grad_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_grad_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_grad_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_int), C.POINTER(i64)] * 2
+    L.sctl_amd_lists_eval_grad_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_lists_eval_grad_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci]
+    L.sctl_amd_eval_lists_grad_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, ci]
     L.sctl_amd_near_apply_transpose_host.argtypes = [vp, vp, vp]
     L.sctl_amd_near_apply_transpose_device.argtypes = [vp, vp, vp, vp]
     L.sctl_amd_op_eval_transpose.argtypes = [vp, vp, vp, ci, ci, vp, ci]
@@ -733,6 +737,11 @@ class GenericKernel:
             return eval_grad_host(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
         return eval_grad_device(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
 
+    def EvalListsGrad(self, r_trg, r_src, n_src, v_src, w_trg, trg_off, trg_cnt, src_off, src_cnt, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
+        """EvalGrad over P2P lists (sctl_amd_eval_lists_grad_host): returns (g_trg, g_src, g_nrm)."""
+        return eval_lists_grad_host(self._info["id"], trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits,
+                                    ctx=self._ctx, **kw)
+
     def EvalGradDensities(self, r_trg, r_src, n_src, V_src, W_trg, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
         if isinstance(r_trg, np.ndarray):
             return eval_grad_densities_host(self._info["id"], r_trg, r_src, n_src, V_src, W_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
@@ -1141,6 +1150,42 @@ class ListsPlan:
                    "lists_eval_transpose_device")
         return g_src
 
+    def eval_grad_host(self, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1):
+        """Gradients of L = sum over the lists of <w_trg, A_l v_src> with respect to the target coordinates, the source coordinates and the source
+        normals on numpy arrays (sctl_amd_lists_eval_grad_host).  `want` names the outputs to compute, of "trg", "src", "nrm" (default: all the
+        kernel has), as sctl_amd.eval_grad_host does; "trg" needs a plan with the forward direction, "src" and "nrm" one with the transposed.
+        Returns (g_trg, g_src, g_nrm), each Nt*3 or Ns*3 values, None where not wanted; an output of the right size is accumulated into, any
+        other size (or None) gives a fresh zeroed result."""
+        dt, i = self.dtype, self.info
+        out = []
+        for wanted, g, n in zip(_grad_wanted(i, want), (g_trg, g_src, g_nrm), (self.Nt * 3, self.Ns * 3, self.Ns * 3)):
+            out.append(None if not wanted else g if g is not None and g.size == n else np.zeros(n, dtype=dt))
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        ptr = [None if g is None else _np_ptr(g, dt, g.size, what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+        _check(lib().sctl_amd_lists_eval_grad_host(self._h, _np_ptr(r_trg, dt, self.Nt * 3, "r_trg"), _np_ptr(r_src, dt, self.Ns * 3, "r_src"),
+                                                   _np_ptr(n_src, dt, self.Ns * i["nd"], "n_src"), _np_ptr(v_src, dt, self.Ns * i["k0"], "v_src"),
+                                                   _np_ptr(w_trg, dt, self.Nt * i["k1"], "w_trg"), ptr[0], ptr[1], ptr[2], digits, cp, cb), "lists_eval_grad_host")
+        return tuple(out)
+
+    def eval_grad_device(self, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1, stream=None):
+        """The same on torch CUDA tensors on the plan's device (sctl_amd_lists_eval_grad_device), enqueued on `stream` (default: torch's current
+        stream): one launch for g_trg, one for g_src and g_nrm; outputs of the right size are accumulated into."""
+        import torch
+        i = self.info
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        out = []
+        for wanted, g, n in zip(_grad_wanted(i, want), (g_trg, g_src, g_nrm), (self.Nt * 3, self.Ns * 3, self.Ns * 3)):
+            out.append(None if not wanted else g if g is not None and g.numel() == n else torch.zeros(n, dtype=tdt, device=r_trg.device))
+        keep, cp, cb = _ctx_blob(i, self.ctx)
+        ptr = [None if g is None else _t_ptr(g, tdt, g.numel(), what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+        with torch.cuda.device(r_trg.device):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            _check(lib().sctl_amd_lists_eval_grad_device(self._h, _t_ptr(r_trg, tdt, self.Nt * 3, "r_trg"), _t_ptr(r_src, tdt, self.Ns * 3, "r_src"),
+                                                         _t_ptr(n_src, tdt, self.Ns * i["nd"], "n_src"), _t_ptr(v_src, tdt, self.Ns * i["k0"], "v_src"),
+                                                         _t_ptr(w_trg, tdt, self.Nt * i["k1"], "w_trg"), ptr[0], ptr[1], ptr[2], digits, cp, cb,
+                                                         C.c_void_p(st.cuda_stream)), "lists_eval_grad_device")
+        return tuple(out)
+
     def eval_host(self, r_trg, r_src, n_src, v_src, v_trg=None, digits=-1):
         """numpy arrays; v_trg of the right size is accumulated into, otherwise a fresh zeroed result is returned."""
         dt, i = self.dtype, self.info
@@ -1293,6 +1338,29 @@ def eval_lists_transpose_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r
         return plan.eval_transpose_host(r_trg, r_src, n_src, w_trg, g_src, digits)
     finally:
         plan.close()
+
+
+def eval_lists_grad_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=None, g_nrm=None, want=None, digits=-1,
+                         ctx=None, device=0):
+    """One-shot sctl_amd_eval_lists_grad_host: both directions planned, the wanted gradients evaluated, the plan released.  Arguments and result as
+    ListsPlan.eval_grad_host."""
+    info = kernel_info(name)
+    dt = np.dtype(r_trg.dtype)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (trg_off, trg_cnt, src_off, src_cnt)]
+    if len({a.size for a in arrs}) != 1:
+        raise SctlAmdError("the four list arrays must have one entry per list")
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    out = []
+    for wanted, g, n in zip(_grad_wanted(info, want), (g_trg, g_src, g_nrm), (Nt * 3, Ns * 3, Ns * 3)):
+        out.append(None if not wanted else g if g is not None and g.size == n else np.zeros(n, dtype=dt))
+    keep, cp, cb = _ctx_blob(info, ctx)
+    ptr = [None if g is None else _np_ptr(g, dt, g.size, what) for g, what in zip(out, ("g_trg", "g_src", "g_nrm"))]
+    _check(lib().sctl_amd_eval_lists_grad_host(info["id"], _real_of(dt), arrs[0].size, p(arrs[0]), p(arrs[1]), p(arrs[2]), p(arrs[3]), Nt, Ns,
+                                               _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"), _np_ptr(n_src, dt, Ns * info["nd"], "n_src"),
+                                               _np_ptr(v_src, dt, Ns * info["k0"], "v_src"), _np_ptr(w_trg, dt, Nt * info["k1"], "w_trg"), ptr[0], ptr[1], ptr[2],
+                                               digits, cp, cb, device), "eval_lists_grad_host")
+    return tuple(out)
 
 
 def eval_lists_transpose_densities_host(name, trg_off, trg_cnt, src_off, src_cnt, r_trg, r_src, n_src, W_trg, G_src=None, digits=-1, ctx=None, device=0):

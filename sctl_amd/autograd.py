@@ -29,6 +29,11 @@ plan.eval_transpose_device; densities only.
     u = sctl_amd.autograd.lists_sum(plan, r_trg, r_src, None, v_src)
     u.square().sum().backward()                                                      # v_src.grad = sum over the lists of A_l^T (2 u)
 
+lists_sum_geometry differentiates the geometry of such a sum as well: its backward adds plan.eval_grad_device (sctl_amd_lists_eval_grad_device), one launch
+per side, for whichever of r_trg, r_src, n_src need a gradient.
+
+    u = sctl_amd.autograd.lists_sum_geometry(plan, x, x, None, v_src)                # x.requires_grad: x.grad = g_trg + g_src
+
 lists_sum_densities is lists_sum for several densities: the forward is plan.eval_densities_device, the backward
 plan.eval_transpose_densities_device, all gradient rows in one launch per pass; densities only.
 
@@ -205,6 +210,50 @@ def lists_sum(plan, r_trg, r_src, n_src, v_src, digits=-1):
         if t is not None and t.requires_grad:
             raise api.SctlAmdError("lists_sum differentiates with respect to the densities only: %s requires grad" % what)
     return _ListsSum.apply(plan, r_trg, r_src, n_src, v_src, digits)
+
+
+class _ListsSumGeometry(torch.autograd.Function):
+    @staticmethod
+    def forward(fn_ctx, plan, r_trg, r_src, n_src, v_src, digits):
+        fn_ctx.plan, fn_ctx.digits = plan, digits
+        # one tensor for both point sets stays one tensor (one address): the list kernels then know that every box meets its own points
+        same = r_src is r_trg or (r_src.data_ptr() == r_trg.data_ptr() and r_src.shape == r_trg.shape)
+        r_trg = r_trg.detach().contiguous()
+        r_src = r_trg if same else r_src.detach().contiguous()
+        v_src = v_src.detach().contiguous()
+        n_src = None if n_src is None else n_src.detach().contiguous()
+        fn_ctx.same, fn_ctx.has_normal = same, n_src is not None
+        fn_ctx.shapes = (r_trg.shape, r_src.shape, None if n_src is None else n_src.shape)
+        fn_ctx.save_for_backward(*([r_trg, v_src] + ([] if same else [r_src]) + ([n_src] if n_src is not None else [])))
+        return plan.eval_device(r_trg, r_src, n_src, v_src, digits=digits)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fn_ctx, grad_u):
+        saved = list(fn_ctx.saved_tensors)
+        r_trg, v_src = saved[0], saved[1]
+        r_src = r_trg if fn_ctx.same else saved[2]
+        n_src = saved[-1] if fn_ctx.has_normal else None
+        grad_u = grad_u.contiguous()
+        need = fn_ctx.needs_input_grad
+        g_v = fn_ctx.plan.eval_transpose_device(r_trg, r_src, n_src, grad_u, digits=fn_ctx.digits) if need[4] else None
+        want = [what for what, i in (("trg", 1), ("src", 2), ("nrm", 3)) if need[i]]
+        g_trg = g_src = g_nrm = None
+        if want:
+            g = fn_ctx.plan.eval_grad_device(r_trg, r_src, n_src, v_src, grad_u, want=want, digits=fn_ctx.digits)
+            g_trg, g_src, g_nrm = [None if x is None else x.view(shape) for x, shape in zip(g, fn_ctx.shapes)]
+        return None, g_trg, g_src, g_nrm, g_v, None
+
+
+def lists_sum_geometry(plan, r_trg, r_src, n_src, v_src, digits=-1):
+    """plan.eval_device on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to r_trg, r_src, n_src
+    and v_src: the backward is plan.eval_transpose_device for v_src and plan.eval_grad_device — one launch per side, only the sides whose inputs need
+    a gradient — for the geometry.  With one tensor as r_trg and r_src (the self-interaction case) autograd adds the two coordinate gradients.  It
+    runs on the forward's stream, as autograd arranges, and is once-differentiable.  The plan must hold both directions."""
+    both = api.LISTS_FORWARD | api.LISTS_TRANSPOSE
+    if plan.directions != both:
+        raise api.SctlAmdError('lists_sum_geometry needs a ListsPlan made with directions="both": the backward pass walks the transposed work list')
+    return _ListsSumGeometry.apply(plan, r_trg, r_src, n_src, v_src, digits)
 
 
 class _ListsSumDensities(torch.autograd.Function):

@@ -1,0 +1,8 @@
+// Launch table of the list gradient kernels of Helmholtz3D_FxU, both sides (see include/sctl_amd/device/lists_grad_kernel.hpp).
+#include <sctl_amd/device/lists_grad_kernel.hpp>
+namespace sctl_amd {
+const ListsGradEntry& lists_grad_Helmholtz3D_FxU() {
+  static const ListsGradEntry e = make_lists_grad_entry<Helmholtz3D_FxU>();
+  return e;
+}
+}  // namespace sctl_amd

@@ -3,6 +3,7 @@
 // whole waves), orders the work items by cost and keeps them on the device; an evaluation is ONE launch.
 #include "internal.hpp"
 #include "lists_rows_kernel.hpp"
+#include <sctl_amd/device/lists_grad_kernel.hpp>
 #include "workspace.hpp"
 
 #include <algorithm>
@@ -38,8 +39,8 @@ struct sctl_amd_lists {
   ListsSide side[2];      // [0] FORWARD, [1] TRANSPOSE; a side that was not planned stays empty
   // host-pointer evaluation: device copies of the caller's arrays and pinned staging, grown on demand
   hipStream_t st = nullptr;
-  void* dbuf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t dcap[5] = {0, 0, 0, 0, 0};
+  void* dbuf[8] = {};     // [0 .. 4]: lists_host_call; [5 .. 7]: the gradient's g_trg, g_src, g_nrm (lists_grad_host_call)
+  size_t dcap[8] = {};
   char* pinned = nullptr;
   size_t pinned_cap = 0;
 };
@@ -167,6 +168,26 @@ int plan_side(int64_t nlists, const int64_t* own_off, const int64_t* own_cnt, co
   return SCTL_AMD_OK;
 }
 
+// The handle's stream, its device buffers [0, n) grown to bytes[i] and its pinned block grown to hold them all; the plan's device is current.
+int lists_staging(sctl_amd_lists* p, const size_t* bytes, int n) {
+  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  size_t total = 0;
+  for (int i = 0; i < n; i++) {
+    total += Carver::pad(bytes[i]);
+    if (bytes[i] > p->dcap[i]) {
+      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
+      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
+      p->dcap[i] = bytes[i];
+    }
+  }
+  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
+    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
+    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
+    p->pinned_cap = total;
+  }
+  return SCTL_AMD_OK;
+}
+
 // A host-pointer evaluation of nd rows in either direction, after the entry's own checks: device copies of the caller's arrays and pinned staging, kept on
 // the handle and grown on demand.  Slots [0] r_trg, [1] r_src, [2] n_src, [3] nd rows of Ns x K0, [4] nd rows of Nt x K1.  FORWARD sends `in` (v_src) in [3]
 // and returns [4] (v_trg); TRANSPOSE sends `in` (w_trg) in [4] and returns [3] (g_src).  Coordinates and normals go down once, the nd input rows in one
@@ -181,21 +202,7 @@ int lists_host_call(sctl_amd_lists* p, bool transpose, int nd, const void* r_trg
   const void* src[5] = {r_trg, r_src, n_src, transpose ? nullptr : in, transpose ? in : nullptr};
   DeviceScope scope(p->device);
   LISTS_TRY(scope.err);
-  if (!p->st) LISTS_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-  size_t total = 0;
-  for (int i = 0; i < 5; i++) {
-    total += Carver::pad(bytes[i]);
-    if (bytes[i] > p->dcap[i]) {
-      if (p->dbuf[i]) { LISTS_TRY(hipFree(p->dbuf[i])); p->dbuf[i] = nullptr; p->dcap[i] = 0; }
-      LISTS_TRY(hipMalloc(&p->dbuf[i], bytes[i]));
-      p->dcap[i] = bytes[i];
-    }
-  }
-  if (total > p->pinned_cap) {   // every host transfer goes through pinned staging (staging.hpp: PinnedBufT explains why)
-    if (p->pinned) { LISTS_TRY(hipHostFree(p->pinned)); p->pinned = nullptr; p->pinned_cap = 0; }
-    LISTS_TRY(hipHostMalloc((void**)&p->pinned, total, hipHostMallocPortable));
-    p->pinned_cap = total;
-  }
+  if (const int rc = lists_staging(p, bytes, 5)) return rc;
   // the caller's sources ARE its targets (one array): one device copy, which is how the kernel knows that every box meets its own points
   const bool same = r_src == r_trg && bytes[0] == bytes[1];
   Carver cut(p->pinned);
@@ -237,7 +244,8 @@ int sctl_amd_lists_create_directions(int kernel, int real, int device, int64_t n
       return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "list " + std::to_string(l) + " reaches outside the target or source arrays");
   }
   // Each direction checks its own ownership rule only.  The streamed arrays of the forward side are r_src, n_src and v_src, those of the transposed side
-  // r_trg and w_trg: the widest of them bounds the 32-bit byte offsets of the packed form.
+  // r_trg and w_trg: the widest of them bounds the 32-bit byte offsets of the packed form.  The gradient kernels (lists_grad_kernel.hpp) stream the same
+  // arrays side by side: max(3, ND, K0) reals per point on side 0, max(3, K1) on side 1.
   const int64_t rs = (int64_t)real_size(real);
   SidePlan plans[2];
   if (directions & SCTL_AMD_LISTS_FORWARD) {
@@ -618,6 +626,135 @@ int sctl_amd_eval_lists_host(int kernel, int real, int64_t nlists, const int64_t
   int rc = sctl_amd_lists_create(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns, &p);
   if (rc != SCTL_AMD_OK) return rc;
   rc = sctl_amd_lists_eval_host(p, r_trg, r_src, n_src, v_src, v_trg, digits, ctx, ctx_bytes);
+  sctl_amd_lists_destroy(p);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- geometry gradients over the lists (sctl_amd_lists_eval_grad_*, include/sctl_amd/device/lists_grad_kernel.hpp) ------------------------------------
+// g_trg from the plan's FORWARD side (its work items own targets), g_src and g_nrm from its TRANSPOSE side (they own sources): one launch per side, only
+// for the sides whose outputs are asked for.
+namespace sctl_amd {
+namespace {
+// the launch table of a built-in kernel; null for a registered plugin kernel
+const ListsGradEntry* lists_grad_entry(int kernel_id) {
+  if (kernel_id < 0 || kernel_id >= SCTL_AMD_NUM_KERNELS) return nullptr;
+  static const ListsGradEntry* tab[SCTL_AMD_NUM_KERNELS] = {
+      &lists_grad_Laplace3D_FxU(), &lists_grad_Laplace3D_DxU(), &lists_grad_Laplace3D_FxdU(),  &lists_grad_Stokes3D_FxU(),      &lists_grad_Stokes3D_DxU(),
+      &lists_grad_Stokes3D_FxT(),  &lists_grad_Stokes3D_FSxU(), &lists_grad_Stokes3D_FxUP(), &lists_grad_Laplace3D_FDxUdU(), &lists_grad_Helmholtz3D_FxU()};
+  return tab[kernel_id];
+}
+
+// the checks both entries make, in the order of sctl_amd_lists_eval_transpose_*: the handle, the directions, the context
+int check_lists_grad(const sctl_amd_lists* p, const void* g_trg, const void* g_src, const void* g_nrm, const void* ctx, int ctx_bytes) {
+  if (!p) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null handle");
+  const KernelEntry& k = *p->k;
+  if (!lists_grad_entry(k.id))
+    return set_error(SCTL_AMD_ERR_UNKNOWN_KERNEL, std::string(k.name) + " is a plugin kernel: gradients over lists are built for the built-in kernels only");
+  if (g_trg && !(p->directions & SCTL_AMD_LISTS_FORWARD))
+    return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "g_trg comes from the FORWARD direction, which this plan was not made for: plan with SCTL_AMD_LISTS_FORWARD");
+  if ((g_src || g_nrm) && !(p->directions & SCTL_AMD_LISTS_TRANSPOSE))
+    return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "g_src and g_nrm come from the TRANSPOSE direction, which this plan was not made for: plan with SCTL_AMD_LISTS_TRANSPOSE");
+  if (g_nrm && k.nd == 0) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, std::string(k.name) + " has no source normal: g_nrm must be null");
+  return check_ctx(k, ctx, ctx_bytes);
+}
+// does side d of the plan have anything to launch for these outputs
+bool lists_grad_side(const sctl_amd_lists* p, int d, const void* g_trg, const void* g_src, const void* g_nrm) {
+  return (d == 0 ? g_trg != nullptr : (g_src || g_nrm)) && p->side[d].nitems > 0;
+}
+
+// The host-pointer form, after the entry's checks: lists_host_call's slots [0 .. 4] carry the five inputs down, [5 .. 7] bring the wanted outputs back.
+int lists_grad_host_call(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, const void* w_trg, void* g_trg,
+                         void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes) {
+  const KernelEntry& k = *p->k;
+  const size_t rs = real_size(p->real);
+  void* const out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, g_trg, g_src, g_nrm};
+  const void* const src[5] = {r_trg, r_src, n_src, v_src, w_trg};
+  const int64_t out_n[8] = {0, 0, 0, 0, 0, p->Nt * 3, p->Ns * 3, p->Ns * 3};
+  size_t bytes[8] = {(size_t)p->Nt * 3 * rs, (size_t)p->Ns * 3 * rs, (size_t)p->Ns * k.nd * rs, (size_t)p->Ns * k.k0 * rs, (size_t)p->Nt * k.k1 * rs, 0, 0, 0};
+  for (int i = 5; i < 8; i++) bytes[i] = out[i] ? (size_t)out_n[i] * rs : 0;
+  DeviceScope scope(p->device);
+  LISTS_TRY(scope.err);
+  if (const int rc = lists_staging(p, bytes, 8)) return rc;
+  const bool same = r_src == r_trg && bytes[0] == bytes[1];   // one array: one device copy, which is how the kernel knows that every box meets its own points
+  Carver cut(p->pinned);
+  char* back[8] = {};
+  for (int i = 0; i < 8; i++) {
+    char* q = cut.take<char>(bytes[i]);
+    if (!bytes[i] || (i == 1 && same)) continue;
+    if (i >= 5) {
+      back[i] = q;
+      LISTS_TRY(hipMemsetAsync(p->dbuf[i], 0, bytes[i], p->st));
+    } else {
+      std::memcpy(q, src[i], bytes[i]);
+      LISTS_TRY(hipMemcpyAsync(p->dbuf[i], q, bytes[i], hipMemcpyHostToDevice, p->st));
+    }
+  }
+  const int rc = sctl_amd_lists_eval_grad_device(p, p->dbuf[0], same ? p->dbuf[0] : p->dbuf[1], p->dbuf[2], p->dbuf[3], p->dbuf[4], g_trg ? p->dbuf[5] : nullptr,
+                                                 g_src ? p->dbuf[6] : nullptr, g_nrm ? p->dbuf[7] : nullptr, digits, ctx, ctx_bytes, p->st);
+  if (rc != SCTL_AMD_OK) return rc;
+  for (int i = 5; i < 8; i++)
+    if (back[i]) LISTS_TRY(hipMemcpyAsync(back[i], p->dbuf[i], bytes[i], hipMemcpyDeviceToHost, p->st));
+  LISTS_TRY(hipStreamSynchronize(p->st));
+  for (int i = 5; i < 8; i++)
+    if (back[i]) add_into(p->real, out[i], back[i], out_n[i]);
+  return SCTL_AMD_OK;
+}
+}  // namespace
+}  // namespace sctl_amd
+
+extern "C" {
+
+int sctl_amd_lists_eval_grad_device(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, const void* w_trg, void* g_trg,
+                                    void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  if (const int rc = check_lists_grad(p, g_trg, g_src, g_nrm, ctx, ctx_bytes)) return rc;
+  const bool run[2] = {lists_grad_side(p, 0, g_trg, g_src, g_nrm), lists_grad_side(p, 1, g_trg, g_src, g_nrm)};
+  if (!run[0] && !run[1]) return SCTL_AMD_OK;
+  const KernelEntry& k = *p->k;
+  if (!r_trg || !r_src || !v_src || !w_trg || (k.nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or weight array");
+  const ListsGradEntry& ge = *lists_grad_entry(k.id);
+  DeviceScope scope(p->device);      // the work lists live on the plan's device
+  LISTS_TRY(scope.err);
+  const int mode = mode_for(p->real, digits);
+  const double scale = k.scale / ge.grad_factor[mode];
+  for (int d = 0; d < 2; d++) {
+    if (!run[d]) continue;
+    const ListsSide& sd = p->side[d];
+    (void)hipGetLastError();
+    with_real(p->real, [&](auto zero) {
+      using R = decltype(zero);
+      ListGArgs<R> a{{0}, (const ListItem*)sd.d_items, (const ListRange*)sd.d_ranges, (const R*)(d ? r_src : r_trg), (const R*)(d ? r_trg : r_src), (const R*)n_src,
+                     (const R*)v_src, (const R*)w_trg, (R*)(d ? g_src : g_trg), (R*)(d ? g_nrm : nullptr), (R)scale, make_ctx(k, ctx),
+                     (const PackedGroup*)sd.d_groups, (const uint32_t*)sd.d_flat};
+      std::memcpy(a.xcd_first, sd.xcd_first, sizeof a.xcd_first);
+      if constexpr (std::is_same<R, double>::value) ge.f64[mode][d](a, sd.nblocks, (hipStream_t)stream);
+      else ge.f32[mode][d](a, sd.nblocks, (hipStream_t)stream);
+      return 0;
+    });
+    LISTS_TRY(hipGetLastError());
+    count_work(sd.pairs, k);
+  }
+  return SCTL_AMD_OK;
+}
+
+int sctl_amd_lists_eval_grad_host(sctl_amd_lists* p, const void* r_trg, const void* r_src, const void* n_src, const void* v_src, const void* w_trg, void* g_trg,
+                                  void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes) {
+  if (const int rc = check_lists_grad(p, g_trg, g_src, g_nrm, ctx, ctx_bytes)) return rc;
+  if (!lists_grad_side(p, 0, g_trg, g_src, g_nrm) && !lists_grad_side(p, 1, g_trg, g_src, g_nrm)) return SCTL_AMD_OK;
+  if (!r_trg || !r_src || !v_src || !w_trg || (p->k->nd > 0 && !n_src)) return set_error(SCTL_AMD_ERR_BAD_ARGUMENT, "null coordinate, normal, density or weight array");
+  return lists_grad_host_call(p, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits, ctx, ctx_bytes);
+}
+
+// one-shot form: plan both directions, evaluate, release
+int sctl_amd_eval_lists_grad_host(int kernel, int real, int64_t nlists, const int64_t* trg_off, const int64_t* trg_cnt, const int64_t* src_off,
+                                  const int64_t* src_cnt, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                                  const void* w_trg, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, int ctx_bytes, int device) {
+  sctl_amd_lists* p = nullptr;
+  int rc = sctl_amd_lists_create_directions(kernel, real, device, nlists, trg_off, trg_cnt, src_off, src_cnt, Nt, Ns,
+                                            SCTL_AMD_LISTS_FORWARD | SCTL_AMD_LISTS_TRANSPOSE, &p);
+  if (rc != SCTL_AMD_OK) return rc;
+  rc = sctl_amd_lists_eval_grad_host(p, r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits, ctx, ctx_bytes);
   sctl_amd_lists_destroy(p);
   return rc;
 }
