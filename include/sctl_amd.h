@@ -317,6 +317,33 @@ int sctl_amd_eval_grad_densities_host(int kernel, int real, int nd, int64_t Nt, 
 int sctl_amd_eval_grad_densities_plan(int kernel, int real, int nd, int64_t Nt, int64_t Ns, int digits, int* rows_per_pass, int* passes, int* trg_splits,
                                       int64_t* trg_workspace_bytes, int* src_splits, int64_t* src_workspace_bytes);
 
+/* ---- directional derivative (tangent) of v_trg = A v_src along a perturbation of the geometry ------------------------------------------- */
+/* The forward-mode counterpart of sctl_amd_eval_grad_*.  With d = x_t - x_s, a perturbation d_trg of the target coordinates (Nt x 3), d_src of the
+ * source coordinates (Ns x 3) and d_nrm of the source normals (Ns x NormalDim), and the densities held fixed, these entries add the tangent of the
+ * whole field:
+ *     dv_trg[t*TrgDim + k1] += scale * sum_s sum_k0 [(e . grad_d) U(d, n_s) + (d_nrm_s . grad_n) U(d, n_s)][k0][k1] * v_src[s*SrcDim + k0],
+ *     e = d_trg[t] - d_src[s],
+ * scaled as sctl_amd_eval_* scales v_trg — J delta for Gauss-Newton and Newton-Krylov on shapes and placements, the linearisation of a boundary
+ * integral about a moving surface, the sensitivity of a field to one design parameter; <w, dv_trg> = <g_trg, d_trg> + <g_src, d_src> + <g_nrm, d_nrm>
+ * with the outputs of sctl_amd_eval_grad_* for the weights w.  The tangent with respect to the densities is A dv_src: the caller adds it with
+ * sctl_amd_eval_device into the same array.  Any of the three tangents may be null and is then a field of zeros (bit for bit the call with an array
+ * of zeros in its place); with all three null nothing is launched.  d_nrm non-null for a kernel without a normal is SCTL_AMD_ERR_BAD_ARGUMENT.  A
+ * coincident pair contributes 0; Helmholtz: v_src, dv_trg are (re, im) pairs, and k is not differentiated.  `digits`, `ctx` and the argument checks
+ * are those of the forward entries, and they come before any device work.  The exact all-pairs scheme on one device (csrc/jvp_kernel.hpp): the
+ * targets own the sums, the sources stream; sums in a fixed order, no atomics, bit-reproducible.  Counters grow by Nt*Ns pairs.  Nt == 0 or Ns == 0:
+ * nothing is read or written.  Built for the ten built-in kernels: a registered (plugin) kernel is SCTL_AMD_ERR_UNKNOWN_KERNEL here only.  Not
+ * provided: the P2P lists, several density rows in one pass, plugin kernels, the operator handle and any multi-GPU form. */
+/* DEVICE arrays; enqueued on `stream`; dv_trg is accumulated into. */
+int sctl_amd_eval_jvp_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                             const void* d_trg, const void* d_src, const void* d_nrm, void* dv_trg, int digits, const void* ctx, int ctx_bytes, void* stream);
+/* HOST arrays, one device; returns when dv_trg is final.  accumulate != 0 adds to it, 0 overwrites it. */
+int sctl_amd_eval_jvp_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                           const void* d_trg, const void* d_src, const void* d_nrm, void* dv_trg, int accumulate, int digits, const void* ctx, int ctx_bytes,
+                           int device);
+/* The plan of such a call (no side effects, no GPU needed): targets per lane, splits of the source range, and the bytes of partial sums of one launch
+ * (TrgDim sums per target).  Those stay within 2 GB: the targets are cut into several launches rather than the sources into fewer splits. */
+int sctl_amd_eval_jvp_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* trg_per_lane, int* splits, int64_t* workspace_bytes);
+
 /* ---- rank-parallel evaluation: one process per GPU (ParticleFMM::EvalDirect under MPI, fmm-wrapper.txx:504-561) --------------- */
 /* The reference partitions targets and sources over MPI ranks and rotates the source blocks round a ring (:537-558).  Here every
  * rank keeps ITS targets, and the sources (and, per evaluation, the densities) of ALL ranks are all-gathered into each rank's

@@ -46,6 +46,16 @@
 //                              masking and grad_factor as pair_g; what does not depend on the rows is done once per pair.  phi is bilinear in (f, w), so the rows
 //                              are first contracted into the block C = sum_m f_m (x) w_m (contract_rows) and <U, C> is differentiated once — except the
 //                              traction kernel, whose rank-one terms run row by row (DESIGN.md §4.16 has the counts).
+// and the tangent form used by sctl_amd/csrc/jvp_kernel.hpp (the forward-mode twin of pair_g: the derivative of the pair's K1 values along a perturbation of
+// the geometry, the densities held fixed):
+//   pair_j<R,MODE,MASKED[,VARIANT]>(acc, d, e, n, m, f, ctx, K)   acc[k1] += sum_k0 [(e.grad_d) U(d, n) + (m.grad_n) U(d, n)][k0][k1] f[k0], with the SAME
+//                              d = x_trg - x_src as pair(), e = delta d = delta x_trg - delta x_src and m = delta n_src (R[3], or R[1] unused when ND == 0);
+//                              n and f[K0] are the plain inputs.  phi of pair_g is linear in w, so acc[k1] is the coefficient of w[k1] in
+//                              grad_d phi . e + grad_n phi . m: the same powers of y = 1/r, hence the same root (rsqrt_grad: the NORMALISED rsqrt_masked, fp32
+//                              always refined), the same masking (a coincident pair adds 0) and the same grad_factor(mode) as pair_g.  Helmholtz takes G from
+//                              pair()'s tables and variants; the wavenumber is not differentiated.  One exception to the root: the fp32 form of
+//                              Laplace3D_FDxUdU, the only tangent that rises to y^7, takes r^2, one Newton step from the masked fp32 seed and y^2, y^3 in
+//                              fp64, whatever the mode (the comment there).  DESIGN.md §4.18 has the forms and the counts.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -409,6 +419,16 @@ template <class R> __device__ __forceinline__ void stokeslet_grad(R (&G)[3], con
   for (int j = 0; j < 3; j++) G[j] = fma_(y3, fma_(B, f[j], fma_(A, w[j], -(c * d[j]))), G[j]);
 }
 
+// The tangent of the Stokeslet family, u_k = f_k y + A d_k y^3 with A linear in d and dA = e.f (three components): with eps = d.e,
+//   du_k = y^3 (A e_k + (e.f) d_k - eps (f_k + 3 A y^2 d_k))
+template <class R> __device__ __forceinline__ void stokeslet_jvp(R* acc, const R (&d)[3], const R (&e)[3], R y, const R* f, R A, R ef) {
+  const R y2 = y * y, y3 = y2 * y;
+  const R eps = dot3(d, e);
+  const R c = fma_((A * R(3)) * y2, eps, -ef);
+#pragma unroll
+  for (int j = 0; j < 3; j++) acc[j] = fma_(y3, fma_(A, e[j], -fma_(c, d[j], eps * f[j])), acc[j]);
+}
+
 // ---- gradient forms of several density / weight rows (pair_gm of every struct below) --------------------------------------------------------
 // Every phi is bilinear in (f, w), so the sum over rows of phi(f_m, w_m) is the single pair's form on the K0 x K1 block C = sum_m f_m (x) w_m:
 // C[a][b] += f[m][a] w[m][b] over the leading A x B corner of the rows, M FMAs per entry.
@@ -506,6 +526,11 @@ struct Laplace3D_FxU {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(-t, d[j], G[j]);
   }
+  // tangent: u = f y, du = -f y^3 (d.e)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    acc[0] = fma_(-(f[0] * ((y * y) * y)), dot3(d, e), acc[0]);
+  }
   // gradient, several rows: the scalar c = sum_m w_m f_m (M instructions), then pair_g with c for w f
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
@@ -563,6 +588,14 @@ struct Laplace3D_DxU {
 #pragma unroll
       for (int j = 0; j < 3; j++) N[j] = fma_(a, d[j], N[j]);
     }
+  }
+  // tangent: u = f (d.n) y^3, du = f y^3 (e.n + d.m - 3 (d.n) (d.e) y^2)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R a = f[0] * (y2 * y);
+    const R s = fma_((dot3(d, n) * R(-3)) * y2, dot3(d, e), dot3(e, n) + dot3(d, m));
+    acc[0] = fma_(a, s, acc[0]);
   }
   // gradient, several rows: the scalar c = sum_m w_m f_m (M instructions), then pair_g with c for w f
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
@@ -630,6 +663,15 @@ struct Laplace3D_FxdU {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(a, w[j], fma_(b, d[j], G[j]));
   }
+  // tangent: u_k = f d_k y^3, du_k = f y^3 (e_k - 3 (d.e) y^2 d_k)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R a = f[0] * (y2 * y);
+    const R b = (dot3(d, e) * R(-3)) * y2;
+#pragma unroll
+    for (int j = 0; j < 3; j++) acc[j] = fma_(a, fma_(b, d[j], e[j]), acc[j]);
+  }
   // gradient, several rows: the 3-vector v = sum_m f_m w_m (3 M instructions), then pair_g with f = 1 and w = v
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
@@ -691,6 +733,11 @@ struct Stokes3D_FxU {
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, dot3(d, f), dot3(d, w), dot3(f, w));
+  }
+  // tangent: u_k = f_k y + (d.f) d_k y^3 (stokeslet_jvp)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    stokeslet_jvp(acc, d, e, y, f, dot3(d, f), dot3(e, f));
   }
   // gradient, several rows: the 3 x 3 block C = sum_m f_m (x) w_m (9 M instructions), then stokeslet_grad_c
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
@@ -765,6 +812,17 @@ struct Stokes3D_DxU {
 #pragma unroll
       for (int j = 0; j < 3; j++) N[j] = fma_(t, d[j], N[j]);
     }
+  }
+  // tangent: u_k = a b d_k y^5 with a = d.n, b = d.f: du_k = y^5 (ab e_k + ((e.n + d.m) b + a (e.f) - 5 ab (d.e) y^2) d_k)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    const R a = dot3(d, n), b = dot3(d, f), ab = a * b;
+    const R da = dot3(e, n) + dot3(d, m);
+    const R c = fma_(ab * dot3(d, e), y2 * R(-5), fma_(da, b, a * dot3(e, f)));
+#pragma unroll
+    for (int j = 0; j < 3; j++) acc[j] = fma_(y5, fma_(ab, e[j], c * d[j]), acc[j]);
   }
   // gradient, several rows: the 3 x 3 block C = sum_m f_m (x) w_m (9 M instructions); phi = a q y^5 with a = d.n, q = d^T C d and u = (C + C^T) d = grad q:
   //   grad_d = y^5 (q n + a u - 5 a q y^2 d), grad_n = q y^5 d
@@ -890,6 +948,20 @@ struct Stokes3D_FxT {
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(y5, fma_(q, f[j], fma_(A, v[j], e * d[j])), G[j]);
   }
+  // tangent: u_jk = A d_j d_k y^5 with A = d.f: du_jk = y^5 (g_j d_k + A d_j e_k), g = (e.f - 5 A (d.e) y^2) d + A e
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R y2 = y * y;
+    const R y5 = (y2 * y2) * y;
+    const R A = dot3(d, f);
+    const R c = fma_(A * dot3(d, e), y2 * R(-5), dot3(e, f));
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const R g = fma_(c, d[j], A * e[j]), Ad = A * d[j];
+#pragma unroll
+      for (int k = 0; k < 3; k++) acc[j * 3 + k] = fma_(y5, fma_(g, d[k], Ad * e[k]), acc[j * 3 + k]);
+    }
+  }
   // gradient, several rows: the rank-one terms row by row (the block f (x) w has 3 x 6 distinct entries: contracting it first costs about 21 M + 80
   // instructions and 18 more registers against 29 M + 26 here: 164 against 142 at M = 4).  Per row v, q and A as in pair_g, summed unscaled; y^5 and
   // y^2 applied once.
@@ -981,6 +1053,11 @@ struct Stokes3D_FSxU {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, fma_(d[2], f[2], fma_(d[1], f[1], fma_(d[0], f[0], f[3]))), dot3(d, w), dot3(w, f));
   }
+  // tangent: the Stokeslet's with A = (d.f) + f_3; e.f over the three force components (stokeslet_jvp)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    stokeslet_jvp(acc, d, e, y, f, fma_(d[2], f[2], fma_(d[1], f[1], fma_(d[0], f[0], f[3]))), dot3(e, f));
+  }
   // gradient, several rows: the 4 x 3 block C = sum_m f_m (x) w_m (12 M instructions); its last row is the source / sink's s (stokeslet_grad_c)
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
@@ -1056,6 +1133,14 @@ struct Stokes3D_FxUP {
   template <class R, int MODE, bool MASKED, bool WANT_N> static __device__ __forceinline__ void pair_g(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[K0], const R (&w)[K1], const KerCtx&, const Consts<R>& K) {
     const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
     stokeslet_grad(G, d, y, f, w, dot3(d, f), fma_(d[2], w[2], fma_(d[1], w[1], fma_(d[0], w[0], w[3]))), dot3(f, w));
+  }
+  // tangent: the velocity as the Stokeslet (stokeslet_jvp); the pressure p = A y^3 with A = d.f: dp = y^3 (e.f - 3 A (d.e) y^2)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+    const R A = dot3(d, f), ef = dot3(e, f);
+    stokeslet_jvp(acc, d, e, y, f, A, ef);
+    const R y2 = y * y;
+    acc[3] = fma_(y2 * y, fma_((A * R(-3)) * y2, dot3(d, e), ef), acc[3]);
   }
   // gradient, several rows: the 3 x 4 block C = sum_m f_m (x) w_m (12 M instructions); its last column is the pressure's s (stokeslet_grad_c)
   template <class R, int MODE, bool MASKED, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&N)[ND ? 3 : 1], const R (&d)[3], const R (&n)[ND ? 3 : 1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx&, const Consts<R>& K) {
@@ -1196,6 +1281,38 @@ struct Laplace3D_FDxUdU {
 #pragma unroll
       for (int j = 0; j < 3; j++) N[j] = fma_(mu3, fma_(e, d[j], wg[j]), N[j]);
     }
+  }
+  // tangent: with q = f[0], mu = f[1], dn = d.n, eps = d.e, t = e.n + d.m and h = 3 y^2 the potential u = q y + mu dn y^3 and the gradient
+  // g = y^3 (mu n - q d) - mu dn h y^3 d move by
+  //   du = y^3 (mu (t - dn eps h) - q eps)
+  //   dg = y^3 (mu m - (q + mu h dn) e - mu eps h n + h (q eps - mu t + 5 mu dn eps y^2) d)
+  template <class R, int MODE, bool MASKED> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&n)[ND ? 3 : 1], const R (&m)[ND ? 3 : 1], const R (&f)[K0], const KerCtx&, const Consts<R>& K) {
+    R y2, y3;
+    if constexpr (std::is_same<R, float>::value) {
+      // fp32: this tangent rises to y^7 = y^3 (y^2)^2, and one close pair can hold half of a sum, so the rounding of a Newton-refined fp32 y (about one
+      // ulp) arrived seven-fold in the result (measured, 1100 x 513 points: rel-L2 7.5e-7 where the same formula in torch float32 has 1.0e-7).  r^2 (d is
+      // exact), the Newton step from the masked fp32 seed and the two powers are taken in fp64 (full rate on this device) and rounded once each: ten
+      // fp64 instructions, modes 0 and 1 alike.  A masked seed of 0 stays 0; an unmasked inf gives NaN, which the tile's compare finds.
+      const double r2 = __builtin_fma((double)d[2], (double)d[2], __builtin_fma((double)d[1], (double)d[1], (double)d[0] * (double)d[0]));
+      double yd = (double)rsqrt_masked<0, MASKED>((float)r2, K.rsq);
+      yd = __builtin_fma(yd * __builtin_fma(-(r2 * yd), yd, 1.0), 0.5, yd);
+      const double y2d = yd * yd;
+      y2 = (float)y2d;
+      y3 = (float)(y2d * yd);
+    } else {
+      const R y = rsqrt_grad<MODE, MASKED>(len2(d), K.rsq);
+      y2 = y * y;
+      y3 = y2 * y;
+    }
+    const R q = f[0], mu = f[1];
+    const R dn = dot3(d, n), eps = dot3(d, e), t = dot3(e, n) + dot3(d, m);
+    const R h = y2 * K.c3;
+    const R dne = dn * eps;
+    acc[0] = fma_(y3, fma_(mu, fma_(-dne, h, t), -(q * eps)), acc[0]);
+    const R ce = -fma_(mu * h, dn, q), cn = -((eps * h) * mu);
+    const R cd = h * fma_(mu, fma_(dne * R(5), y2, -t), q * eps);
+#pragma unroll
+    for (int j = 0; j < 3; j++) acc[1 + j] = fma_(y3, fma_(mu, m[j], fma_(ce, e[j], fma_(cn, n[j], cd * d[j]))), acc[1 + j]);
   }
   // gradient, several rows: the 2 x 4 block C = sum_m (q, mu)_m (x) (w_u, w_g)_m (8 M instructions): c_q = C[0][0], c_m = C[1][0], the 3-vectors gq = C[0][1..3]
   // and gm = C[1][1..3].  With dn = d.n, Bq = d.gq, Bm = d.gm the sums of pair_g's terms are
@@ -1364,6 +1481,32 @@ struct Helmholtz3D_FxU {
     const R t = -fma_(R(ctx.v[0]), hi, a * hr) * y;
 #pragma unroll
     for (int j = 0; j < 3; j++) G[j] = fma_(t, d[j], G[j]);
+  }
+  // tangent: u = G f as complex numbers and dG/dr = (ik - 1/r) G, dr = (d.e) y: du = (ik - y) y (d.e) H with H = G f,
+  //   Re((ik - y) H) = -(Im k + y) H_re - (Re k) H_im,    Im((ik - y) H) = (Re k) H_re - (Im k + y) H_im
+  // G from the same tables and variants as pair() and pair_g, with the same grad_factor.
+  template <class R, int MODE, bool MASKED, int VARIANT> static __device__ __forceinline__ void pair_j(R (&acc)[K1], const R (&d)[3], const R (&e)[3], const R (&)[1], const R (&)[1], const R (&f)[K0], const KerCtx& ctx, const Consts<R>& K) {
+    constexpr bool REAL_K = (VARIANT & 1) != 0;
+    const R r2 = len2(d);
+    const R rinv = rsqrt_scaled<MODE, MASKED>(r2, K.rsq);
+    const R rs = r2 * rinv;
+    R gr, gi;
+    if constexpr ((VARIANT & 2) != 0) {
+      cexp_<MASKED, REAL_K>(rs, rinv, ctx, gr, gi, K);
+    } else {
+      const R r = std::is_same<R, double>::value ? rs : rs * R(K.cinv);
+      R sn, cs;
+      sincos_<MASKED>(r, ctx, sn, cs, K);
+      R amp = rinv;
+      if (!REAL_K) amp *= exp_<MASKED>(r, ctx, K);
+      gr = amp * cs; gi = amp * sn;
+    }
+    const R y = rinv * R(K.cinv);
+    const R hr = fma_(-gi, f[1], gr * f[0]), hi = fma_(gr, f[1], gi * f[0]);
+    const R a = REAL_K ? y : y + R(ctx.v[1]);
+    const R t = y * dot3(d, e);
+    acc[0] = fma_(t, -fma_(R(ctx.v[0]), hi, a * hr), acc[0]);
+    acc[1] = fma_(t, fma_(R(ctx.v[0]), hr, -(a * hi)), acc[1]);
   }
   // gradient, several rows: the complex c = sum_m conj(w_m) f_m (4 M instructions), then pair_g's form on it; G and grad_factor as there
   template <class R, int MODE, bool MASKED, int VARIANT, bool WANT_N, int M> static __device__ __forceinline__ void pair_gm(R (&G)[3], R (&)[1], const R (&d)[3], const R (&)[1], const R (&f)[M][K0], const R (&w)[M][K1], const KerCtx& ctx, const Consts<R>& K) {

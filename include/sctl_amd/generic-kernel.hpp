@@ -350,6 +350,34 @@ template <class uKernel> class GenericKernel : public uKernel {
     CheckStatus(rc, "sctl_amd_eval_grad_host");
   }
 
+  // The tangent of v_trg = A v_src along a perturbation of the geometry (sctl_amd_eval_jvp_host; not in the reference): with d = x_t - x_s and
+  // e = d_trg[t] - d_src[s],
+  //   dv_trg[t*TrgDim + k1] += scale sum_s sum_k0 [(e . grad_d) U(d, n_s) + (d_nrm[s] . grad_n) U(d, n_s)][k0][k1] v_src[s*SrcDim + k0].
+  // A null tangent is a field of zeros; d_nrm must be null for a kernel without a normal (here an assertion, as every size check of this class is; the C
+  // entry returns SCTL_AMD_ERR_BAD_ARGUMENT).  The densities are held fixed: their tangent is
+  // Eval(dv_trg, r_trg, r_src, n_src, dv_src).  dv_trg follows Eval's rule: the right size is accumulated into, any other is resized and zeroed.
+  template <class Real, Integer digits = -1>
+  void EvalJvp(Vector<Real>& dv_trg, const Vector<Real>& r_trg, const Vector<Real>& r_src, const Vector<Real>& n_src, const Vector<Real>& v_src,
+               const Vector<Real>* d_trg, const Vector<Real>* d_src, const Vector<Real>* d_nrm) const {
+    const Long Ns = r_src.Dim() / DIM, Nt = r_trg.Dim() / DIM;
+    SCTL_AMD_ASSERT(r_trg.Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(r_src.Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(v_src.Dim() == Ns * KDIM0);
+    SCTL_AMD_ASSERT(n_src.Dim() == Ns * N_DIM || !N_DIM);
+    SCTL_AMD_ASSERT(!d_trg || d_trg->Dim() == Nt * DIM);
+    SCTL_AMD_ASSERT(!d_src || d_src->Dim() == Ns * DIM);
+    SCTL_AMD_ASSERT(!d_nrm || (N_DIM && d_nrm->Dim() == Ns * N_DIM));
+    if (dv_trg.Dim() != Nt * KDIM1) {
+      dv_trg.ReInit(Nt * KDIM1);
+      dv_trg.SetZero();
+    }
+    RequireSupported();
+    const int rc = sctl_amd_eval_jvp_host(DeviceKernelId(), RealTag<Real>::value, Nt, Ns, r_trg.begin(), r_src.begin(), N_DIM ? n_src.begin() : nullptr, v_src.begin(),
+                                          d_trg ? d_trg->begin() : nullptr, d_src ? d_src->begin() : nullptr, d_nrm ? d_nrm->begin() : nullptr, dv_trg.begin(),
+                                          /*accumulate*/ 1, (int)digits, ctx_ptr, (int)uKernel::CTX_BYTES, DeviceSet::Get()[0]);
+    CheckStatus(rc, "sctl_amd_eval_jvp_host");
+  }
+
   // EvalGrad for several density / weight pairs in one evaluation (sctl_amd_eval_grad_densities_host; not in the reference): row m of F (nd x Ns*SrcDim)
   // is a density, row m of W (nd x Nt*TrgDim) its target weights, and the outputs are the gradients of L = sum_m <W[m], A F[m]> — the sums over the rows of
   // what EvalGrad adds, one g_trg, g_src and g_nrm whatever nd is — with the row-independent work of a pair done once for several rows.  The outputs follow

@@ -41,7 +41,8 @@ SYMBOLS = ["sctl_amd_version", "sctl_amd_last_error", "sctl_amd_device_count", "
            "sctl_amd_near_apply_transpose_densities_host", "sctl_amd_near_apply_transpose_densities_device", "sctl_amd_op_eval_transpose_densities",
            "sctl_amd_op_eval_potential_transpose_densities",
            "sctl_amd_eval_grad_densities_device", "sctl_amd_eval_grad_densities_host", "sctl_amd_eval_grad_densities_plan",
-           "sctl_amd_lists_eval_grad_device", "sctl_amd_lists_eval_grad_host", "sctl_amd_eval_lists_grad_host"]
+           "sctl_amd_lists_eval_grad_device", "sctl_amd_lists_eval_grad_host", "sctl_amd_eval_lists_grad_host",
+           "sctl_amd_eval_jvp_device", "sctl_amd_eval_jvp_host", "sctl_amd_eval_jvp_plan"]
 
 
 class SctlAmdError(RuntimeError):
@@ -160,6 +161,9 @@ def lib():
     L.sctl_amd_eval_grad_densities_device.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_eval_grad_densities_host.argtypes = [ci, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     L.sctl_amd_eval_grad_densities_plan.argtypes = [ci, ci, ci, i64, i64, ci] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_int), C.POINTER(i64)] * 2
+    L.sctl_amd_eval_jvp_device.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
+    L.sctl_amd_eval_jvp_host.argtypes = [ci, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
+    L.sctl_amd_eval_jvp_plan.argtypes = [ci, ci, i64, i64, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
     L.sctl_amd_lists_eval_grad_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     L.sctl_amd_lists_eval_grad_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci]
     L.sctl_amd_eval_lists_grad_host.argtypes = [ci, ci, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, ci]
@@ -299,6 +303,13 @@ def plan_grad_densities(name, real, nd, Nt, Ns, digits=-1):
     _check(lib().sctl_amd_eval_grad_densities_plan(kernel_id(name), real, nd, Nt, Ns, digits, *[C.byref(x) for x in v]), "eval_grad_densities_plan")
     return dict(rows_per_pass=v[0].value, passes=v[1].value, trg=dict(splits=v[2].value, workspace_bytes=v[3].value),
                 src=dict(splits=v[4].value, workspace_bytes=v[5].value))
+
+
+def plan_jvp(name, real, Nt, Ns, digits=-1):
+    """Launch plan of a tangent evaluation (sctl_amd_eval_jvp_plan): targets per lane, splits of the source range, partial-sum workspace of one launch."""
+    t, sp, ws = C.c_int(), C.c_int(), C.c_int64()
+    _check(lib().sctl_amd_eval_jvp_plan(kernel_id(name), real, Nt, Ns, digits, C.byref(t), C.byref(sp), C.byref(ws)), "eval_jvp_plan")
+    return dict(per_lane=t.value, splits=sp.value, workspace_bytes=ws.value)
 
 
 def counters():
@@ -576,6 +587,51 @@ def eval_grad_device(name, r_trg, r_src, n_src, v_src, w_trg, g_trg=None, g_src=
     return tuple(out)
 
 
+def eval_jvp_host(name, r_trg, r_src, n_src, v_src, d_trg=None, d_src=None, d_nrm=None, dv_trg=None, digits=-1, ctx=None, device=0, accumulate=True):
+    """The tangent of v_trg = A v_src along a perturbation of the geometry on host (numpy) arrays (sctl_amd_eval_jvp_host): d_trg (Nt*3), d_src (Ns*3)
+    and d_nrm (Ns*NormalDim) perturb the target coordinates, the source coordinates and the source normals; None is a field of zeros, and with all
+    three None nothing is computed.  Returns dv_trg, Nt*TrgDim values: an array of the right size is accumulated into (overwritten with
+    accumulate=False); any other size (or None) gives a fresh zeroed result, as Eval does.  The densities are held fixed: their tangent is
+    eval_host(name, r_trg, r_src, n_src, dv_src, dv_trg)."""
+    info = kernel_info(name)
+    dt = r_trg.dtype
+    real = _real_of(dt)
+    Nt, Ns = r_trg.size // 3, r_src.size // 3
+    if r_trg.size != Nt * 3 or r_src.size != Ns * 3:
+        raise SctlAmdError("coordinate arrays must hold 3 values per point")
+    if dv_trg is None or dv_trg.size != Nt * info["k1"]:
+        dv_trg = np.zeros(Nt * info["k1"], dtype=dt)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    # a normal tangent for a kernel without a normal goes down as it is: the library refuses it
+    tan = [None if a is None else _np_ptr(a, dt, n if n else a.size, what)
+           for a, n, what in ((d_trg, Nt * 3, "d_trg"), (d_src, Ns * 3, "d_src"), (d_nrm, Ns * info["nd"], "d_nrm"))]
+    _check(lib().sctl_amd_eval_jvp_host(info["id"], real, Nt, Ns, _np_ptr(r_trg, dt, Nt * 3, "r_trg"), _np_ptr(r_src, dt, Ns * 3, "r_src"),
+                                        _np_ptr(n_src, dt, Ns * info["nd"], "n_src"), _np_ptr(v_src, dt, Ns * info["k0"], "v_src"), tan[0], tan[1], tan[2],
+                                        _np_ptr(dv_trg, dt, Nt * info["k1"], "dv_trg"), 1 if accumulate else 0, digits, cp, cb, device), "eval_jvp_host")
+    return dv_trg
+
+
+def eval_jvp_device(name, r_trg, r_src, n_src, v_src, d_trg=None, d_src=None, d_nrm=None, dv_trg=None, digits=-1, ctx=None, stream=None):
+    """The same on torch CUDA tensors (sctl_amd_eval_jvp_device), enqueued on `stream` (default: torch's current stream); dv_trg of the right size is
+    accumulated into."""
+    import torch
+    info = kernel_info(name)
+    tdt = r_trg.dtype
+    real = F64 if tdt == torch.float64 else _real_of(np.float32 if tdt == torch.float32 else np.int8)
+    Nt, Ns = r_trg.numel() // 3, r_src.numel() // 3
+    if dv_trg is None or dv_trg.numel() != Nt * info["k1"]:
+        dv_trg = torch.zeros(Nt * info["k1"], dtype=tdt, device=r_trg.device)
+    keep, cp, cb = _ctx_blob(info, ctx)
+    tan = [None if a is None else _t_ptr(a, tdt, n if n else a.numel(), what)
+           for a, n, what in ((d_trg, Nt * 3, "d_trg"), (d_src, Ns * 3, "d_src"), (d_nrm, Ns * info["nd"], "d_nrm"))]
+    with torch.cuda.device(r_trg.device):
+        st = stream if stream is not None else torch.cuda.current_stream()
+        _check(lib().sctl_amd_eval_jvp_device(info["id"], real, Nt, Ns, _t_ptr(r_trg, tdt, Nt * 3, "r_trg"), _t_ptr(r_src, tdt, Ns * 3, "r_src"),
+                                              _t_ptr(n_src, tdt, Ns * info["nd"], "n_src"), _t_ptr(v_src, tdt, Ns * info["k0"], "v_src"), tan[0], tan[1], tan[2],
+                                              _t_ptr(dv_trg, tdt, Nt * info["k1"], "dv_trg"), digits, cp, cb, C.c_void_p(st.cuda_stream)), "eval_jvp_device")
+    return dv_trg
+
+
 def _grad_rows(info, V_src, W_trg, Nt, Ns, dim):
     """the number of rows of V_src (nd, Ns*SrcDim) and W_trg (nd, Nt*TrgDim)"""
     if dim(V_src) != 2 or V_src.shape[1] != Ns * info["k0"]:
@@ -736,6 +792,11 @@ class GenericKernel:
         if isinstance(r_trg, np.ndarray):
             return eval_grad_host(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
         return eval_grad_device(self._info["id"], r_trg, r_src, n_src, v_src, w_trg, g_trg, g_src, g_nrm, digits=digits, ctx=self._ctx, **kw)
+
+    def EvalJvp(self, r_trg, r_src, n_src, v_src, d_trg=None, d_src=None, d_nrm=None, dv_trg=None, digits=-1, **kw):
+        if isinstance(r_trg, np.ndarray):
+            return eval_jvp_host(self._info["id"], r_trg, r_src, n_src, v_src, d_trg, d_src, d_nrm, dv_trg, digits=digits, ctx=self._ctx, **kw)
+        return eval_jvp_device(self._info["id"], r_trg, r_src, n_src, v_src, d_trg, d_src, d_nrm, dv_trg, digits=digits, ctx=self._ctx, **kw)
 
     def EvalListsGrad(self, r_trg, r_src, n_src, v_src, w_trg, trg_off, trg_cnt, src_off, src_cnt, g_trg=None, g_src=None, g_nrm=None, digits=-1, **kw):
         """EvalGrad over P2P lists (sctl_amd_eval_lists_grad_host): returns (g_trg, g_src, g_nrm)."""

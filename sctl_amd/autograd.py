@@ -11,6 +11,11 @@ of r_trg, r_src, n_src need a gradient.
     u = sctl_amd.autograd.kernel_sum_geometry("Laplace3D-DxU", r_trg, r_src, n_src, v_src)   # any of the four may require grad
     u.square().sum().backward()                                                               # r_trg.grad, r_src.grad, n_src.grad, v_src.grad
 
+kernel_sum_geometry also runs in forward mode: the tangent of u along tangents of any of the four is sctl_amd_eval_jvp_device (pair_j) for the geometry
+plus A dv_src.
+
+    u, du = torch.func.jvp(lambda x: sctl_amd.autograd.kernel_sum_geometry("Laplace3D-DxU", x, r_src, n_src, v_src), (r_trg,), (d_trg,))
+
 kernel_sum_densities is kernel_sum for several densities on one geometry: the forward is sctl_amd_eval_densities_device, the backward
 sctl_amd_eval_transpose_densities_device, A^T (dloss/dU) for all rows in one pass; densities only.
 
@@ -149,16 +154,46 @@ def kernel_sum_densities_geometry(name, r_trg, r_src, n_src, V_src, digits=-1, c
     return _KernelSumDensitiesGeometry.apply(name, r_trg, r_src, n_src, V_src, digits, ctx)
 
 
+class _KernelSumTangent(torch.autograd.Function):
+    """The tangent of _KernelSumGeometry as an operation of its own, so that its tensors arrive as plain CUDA tensors under torch.func.jvp as well:
+    eval_jvp_device for the geometry plus eval_device of the density tangent, accumulated into the same tensor.  An absent tangent goes in as null.
+    It has neither a backward nor a jvp of its own: differentiating a tangent again (reverse over forward, forward over forward) raises."""
+    @staticmethod
+    def forward(kernel, r_trg, r_src, n_src, v_src, d_trg, d_src, d_nrm, d_v):
+        name, digits, ctx = kernel
+        flat = lambda t: None if t is None else t.detach().contiguous().view(-1)
+        du = api.eval_jvp_device(name, r_trg, r_src, n_src, v_src, flat(d_trg), flat(d_src), None if n_src is None else flat(d_nrm), digits=digits, ctx=ctx)
+        if d_v is not None:
+            api.eval_device(name, r_trg, r_src, n_src, flat(d_v), du, digits=digits, ctx=ctx)
+        return du
+
+    @staticmethod
+    def setup_context(fn_ctx, inputs, output):
+        pass
+
+
 class _KernelSumGeometry(torch.autograd.Function):
     @staticmethod
-    def forward(fn_ctx, name, r_trg, r_src, n_src, v_src, digits, ctx):
+    def forward(name, r_trg, r_src, n_src, v_src, digits, ctx):      # contiguous tensors: kernel_sum_geometry made them so, once
+        return api.eval_device(name, r_trg.detach(), r_src.detach(), None if n_src is None else n_src.detach(), v_src.detach(), digits=digits, ctx=ctx)
+
+    @staticmethod
+    def setup_context(fn_ctx, inputs, output):      # (forward takes no context: torch.func's transforms need the two apart)
+        name, r_trg, r_src, n_src, v_src, digits, ctx = inputs
         fn_ctx.kernel = (name, digits, ctx)
-        r_trg, r_src, v_src = r_trg.detach().contiguous(), r_src.detach().contiguous(), v_src.detach().contiguous()
-        n_src = None if n_src is None else n_src.detach().contiguous()
+        r_trg, r_src, v_src = r_trg.detach(), r_src.detach(), v_src.detach()      # the tensors the forward ran on (views of them: no copy)
+        n_src = None if n_src is None else n_src.detach()
         fn_ctx.has_normal = n_src is not None
         fn_ctx.shapes = (r_trg.shape, r_src.shape, None if n_src is None else n_src.shape)
-        fn_ctx.save_for_backward(*([r_trg, r_src, v_src] + ([n_src] if n_src is not None else [])))
-        return api.eval_device(name, r_trg, r_src, n_src, v_src, digits=digits, ctx=ctx)
+        saved = [r_trg, r_src, v_src] + ([n_src] if n_src is not None else [])
+        fn_ctx.save_for_backward(*saved)
+        fn_ctx.save_for_forward(*saved)
+
+    @staticmethod
+    def jvp(fn_ctx, _name, d_trg, d_src, d_nrm, d_v, _digits, _ctx):
+        r_trg, r_src, v_src = fn_ctx.saved_tensors[:3]
+        n_src = fn_ctx.saved_tensors[3] if fn_ctx.has_normal else None
+        return _KernelSumTangent.apply(fn_ctx.kernel, r_trg, r_src, n_src, v_src, d_trg, d_src, d_nrm, d_v)
 
     @staticmethod
     @once_differentiable
@@ -179,8 +214,12 @@ class _KernelSumGeometry(torch.autograd.Function):
 
 def kernel_sum_geometry(name, r_trg, r_src, n_src, v_src, digits=-1, ctx=None):
     """GenericKernel::Eval on torch CUDA tensors (a fresh result, Nt*TrgDim values) that autograd can differentiate with respect to r_trg, r_src,
-    n_src and v_src.  The backward runs on the forward's stream, as autograd arranges, and is once-differentiable."""
-    return _KernelSumGeometry.apply(name, r_trg, r_src, n_src, v_src, digits, ctx)
+    n_src and v_src.  The backward runs on the forward's stream, as autograd arranges, and is once-differentiable.  Forward mode
+    (torch.func.jvp, torch.autograd.forward_ad) works too: the tangent is eval_jvp_device for the geometry plus eval_device of the density tangent.
+    The tangent itself is not differentiable: reverse over forward (a backward through the result of a jvp) and forward over forward raise.  A
+    non-contiguous input is copied once, here."""
+    c = lambda t: None if t is None else t.contiguous()
+    return _KernelSumGeometry.apply(name, c(r_trg), c(r_src), c(n_src), c(v_src), digits, ctx)
 
 
 class _ListsSum(torch.autograd.Function):

@@ -153,6 +153,15 @@ int check_grad(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const voi
   if (!has_grad(*k)) return no_grad(*k);
   return SCTL_AMD_OK;
 }
+int check_jvp(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+              const void* d_nrm, const void* dv_trg, int ctx_bytes, const void* ctx) {
+  const int rc = check_common(k, real, Nt, Ns, r_trg, r_src, n_src, ctx_bytes, ctx);
+  if (rc) return rc;
+  if ((Ns > 0 && !v_src) || (Nt > 0 && !dv_trg)) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "null density or tangent result array");
+  if (d_nrm && k->nd == 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, std::string(k->name) + " has no source normal: d_nrm must be null");
+  if (!jvp_entry(k->id)) return no_jvp(*k);
+  return SCTL_AMD_OK;
+}
 int check_grad_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                          const void* v_src, const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx) {
   if (nd < 0) return fail(SCTL_AMD_ERR_BAD_ARGUMENT, "negative number of density and weight rows");
@@ -450,6 +459,29 @@ int sctl_amd_eval_grad_plan(int kernel, int real, int64_t Nt, int64_t Ns, int di
   if (src_per_lane) *src_per_lane = k->grad_t[1];
   if (src_splits) *src_splits = ps.splits;
   if (src_workspace_bytes) *src_workspace_bytes = ps.workspace_bytes;
+  return SCTL_AMD_OK;
+}
+
+// ---- the tangent of v_trg = A v_src along a perturbation of the geometry ----------------------------------------------------------------------
+int sctl_amd_eval_jvp_device(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                             const void* d_trg, const void* d_src, const void* d_nrm, void* dv_trg, int digits, const void* ctx, int ctx_bytes, void* stream) {
+  const KernelEntry* k = registry(kernel);
+  const int rc = check_jvp(k, real, Nt, Ns, r_trg, r_src, n_src, v_src, d_nrm, dv_trg, ctx_bytes, ctx);
+  if (rc) return rc;
+  if (device_count_quiet() <= 0) return no_device();
+  return eval_jvp_device(*k, real, Nt, Ns, r_trg, r_src, n_src, v_src, d_trg, d_src, d_nrm, dv_trg, digits, ctx, (hipStream_t)stream);
+}
+
+int sctl_amd_eval_jvp_plan(int kernel, int real, int64_t Nt, int64_t Ns, int digits, int* trg_per_lane, int* splits, int64_t* workspace_bytes) {
+  const KernelEntry* k = registry(kernel);
+  if (const int rc = check_real_sizes(k, real, Nt, Ns)) return rc;
+  const JvpEntry* je = jvp_entry(k->id);
+  if (!je) return no_jvp(*k);
+  (void)digits;   // every accuracy mode runs the same launch geometry
+  const PlanOwned p = make_plan_j(*k, *je, real, Nt, Ns);
+  if (trg_per_lane) *trg_per_lane = je->t;
+  if (splits) *splits = p.splits;
+  if (workspace_bytes) *workspace_bytes = p.workspace_bytes;
   return SCTL_AMD_OK;
 }
 

@@ -1,6 +1,6 @@
 // Launch planning and the typed launch drivers of the all-pairs evaluators, behind the untyped functions of eval_drivers.hpp: the forward sum, several
-// densities, the transposed sum, several weight vectors through it, the geometry gradients and the kernel matrix.  All arithmetic lives in eval_kernel.hpp /
-// rows_kernel.hpp (several rows, both directions) / multi_grad_kernel.hpp / ukernels.hpp.
+// densities, the transposed sum, several weight vectors through it, the geometry gradients, the tangent along a perturbation of the geometry and the kernel
+// matrix.  All arithmetic lives in eval_kernel.hpp / rows_kernel.hpp (several rows, both directions) / multi_grad_kernel.hpp / jvp_kernel.hpp / ukernels.hpp.
 #include "eval_drivers.hpp"
 #include "workspace.hpp"
 
@@ -556,6 +556,55 @@ int eval_grad_densities_device_t(const KernelEntry& k, int real, int nd, int64_t
 }
 }  // namespace
 
+// ---- the tangent of the field along a perturbation of the geometry (sctl_amd_eval_jvp_*, jvp_kernel.hpp) -----------------------------------------
+const JvpEntry* jvp_entry(int kernel_id) {
+  static const JvpEntry* tab[SCTL_AMD_NUM_KERNELS] = {&jvp_Laplace3D_FxU(), &jvp_Laplace3D_DxU(), &jvp_Laplace3D_FxdU(),   &jvp_Stokes3D_FxU(),
+                                                      &jvp_Stokes3D_DxU(),  &jvp_Stokes3D_FxT(),  &jvp_Stokes3D_FSxU(),    &jvp_Stokes3D_FxUP(),
+                                                      &jvp_Laplace3D_FDxUdU(), &jvp_Helmholtz3D_FxU()};
+  return (kernel_id >= 0 && kernel_id < SCTL_AMD_NUM_KERNELS) ? tab[kernel_id] : nullptr;
+}
+int no_jvp(const KernelEntry& k) {
+  return fail(SCTL_AMD_ERR_UNKNOWN_KERNEL, std::string("kernel '") + k.name + "' has no tangent form: sctl_amd_eval_jvp_* is built for the built-in kernels only");
+}
+PlanOwned make_plan_j(const KernelEntry& k, const JvpEntry& je, int real, int64_t Nt, int64_t Ns) {
+  return plan_owned(Nt, Ns, je.t, 6 + 2 * k.nd + k.k0, k.k1, (int64_t)real_size(real));
+}
+
+namespace {
+template <class R>
+int eval_jvp_device_t(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const R* xt, const R* xs, const R* xn, const R* f, const R* dxt, const R* dxs,
+                      const R* dxn, R* dv, int digits, const void* ctx, hipStream_t st) {
+  if (Nt == 0 || Ns == 0 || (!dxt && !dxs && !dxn)) return SCTL_AMD_OK;   // nothing to add: the tangent along a zero perturbation is zero
+  (void)hipGetLastError();
+  const JvpEntry& je = *jvp_entry(k.id);
+  const PlanOwned p = make_plan_j(k, je, real, Nt, Ns);
+  const int mode = mode_for(real, digits);
+  const R scale = (R)(k.scale / k.grad_factor[mode]);   // pair_j accumulates the multiple pair_g does
+  EvalJLaunch<R> launch;
+  if constexpr (std::is_same<R, double>::value) launch = je.f64[mode];
+  else launch = je.f32[mode];
+  void* ws = nullptr;
+  if (p.splits > 1) HIP_TRY(workspace_acquire(st, (size_t)p.workspace_bytes, &ws));
+  const int64_t group = (int64_t)kBlock * je.t;
+  for (int64_t t0 = 0; t0 < Nt; t0 += p.owners_per_launch) {   // one launch unless the partial sums of all targets would pass 2 GB
+    const int64_t n = (Nt - t0 < p.owners_per_launch) ? Nt - t0 : p.owners_per_launch;
+    EvalJArgs<R> a{};
+    a.Nt = n; a.Ns = Ns; a.xt = xt + t0 * 3; a.dxt = dxt ? dxt + t0 * 3 : nullptr; a.xs = xs; a.dxs = dxs; a.xn = xn; a.dxn = k.nd ? dxn : nullptr; a.f = f;
+    a.dv = dv + t0 * k.k1; a.partial = (R*)ws; a.chunk = p.chunk; a.scale = scale; a.ctx = make_ctx(k, ctx);
+    const dim3 grid((unsigned)((n + group - 1) / group), (unsigned)p.splits);
+    launch(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (p.splits > 1) {
+      const int64_t m = n * k.k1;
+      hipLaunchKernelGGL((reduce_splits_kernel<R>), dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.dv, (const R*)a.partial, m, p.splits, scale);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  count_work(Nt * Ns, k);
+  return SCTL_AMD_OK;
+}
+}  // namespace
+
 // ---- the untyped seam: `real` picks the template here and nowhere else ----------------------------------------------------------------------------
 int eval_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, void* v, int digits,
                 const void* ctx, hipStream_t st, int64_t nt_whole, bool presorted) {
@@ -580,6 +629,10 @@ int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, con
 int eval_grad_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f,
                                const void* w, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st) {
   return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_grad_densities_device_t<R>(k, real, nd, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)f, (const R*)w, (R*)g_trg, (R*)g_src, (R*)g_nrm, digits, ctx, st); });
+}
+int eval_jvp_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* dxt,
+                    const void* dxs, const void* dxn, void* dv, int digits, const void* ctx, hipStream_t st) {
+  return with_real(real, [&](auto zero) { using R = decltype(zero); return eval_jvp_device_t<R>(k, real, Nt, Ns, (const R*)xt, (const R*)xs, (const R*)xn, (const R*)f, (const R*)dxt, (const R*)dxs, (const R*)dxn, (R*)dv, digits, ctx, st); });
 }
 int matrix_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, void* M, int digits, const void* ctx,
                   hipStream_t st) {

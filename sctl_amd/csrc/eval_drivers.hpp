@@ -4,6 +4,7 @@
 #include "internal.hpp"
 #include "rows_kernel.hpp"
 #include "multi_grad_kernel.hpp"
+#include "jvp_kernel.hpp"
 
 namespace sctl_amd {
 // centered.hip
@@ -81,6 +82,13 @@ int multi_g_form(const MultiGEntry& me, int left);  // as multi_form
 // single gradient's.
 PlanOwned make_plan_gm(const KernelEntry& k, int M, int real, int side, int64_t Nt, int64_t Ns);
 
+// ---- the tangent of the field along a perturbation of the geometry (jvp_kernel.hpp) ----
+const JvpEntry* jvp_entry(int kernel_id);           // null for a registered plugin kernel: the tangent is built for the built-in kernels only
+int no_jvp(const KernelEntry& k);                   // sets the error text, returns SCTL_AMD_ERR_UNKNOWN_KERNEL
+// plan_owned with the targets as owners of K1 sums each and the sources streamed as {x, dx, n, dn, f}; the owner cut honours the same bound, and the same
+// lowering variable, as the transposed and the gradient plans
+PlanOwned make_plan_j(const KernelEntry& k, const JvpEntry& je, int real, int64_t Nt, int64_t Ns);
+
 // ---- the tile-centred fast path (centered.hip) ----
 // mode < 0: the mode of the default accuracy request (what an operator handle sorts its targets for)
 bool has_centered_path(const KernelEntry& k, int real, int mode = -1);
@@ -114,6 +122,10 @@ int eval_grad_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, con
 // would run it on the form of 2)
 int eval_grad_densities_device(const KernelEntry& k, int real, int nd, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f,
                                const void* w, void* g_trg, void* g_src, void* g_nrm, int digits, const void* ctx, hipStream_t st);
+// dv[t,k1] += the tangent of v = A f along (dxt, dxs, dxn), the densities held fixed; a null tangent is a field of zeros, and with all three null nothing
+// is launched.  Built-in kernels only (the caller checks jvp_entry)
+int eval_jvp_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, const void* f, const void* dxt,
+                    const void* dxs, const void* dxn, void* dv, int digits, const void* ctx, hipStream_t st);
 int matrix_device(const KernelEntry& k, int real, int64_t Nt, int64_t Ns, const void* xt, const void* xs, const void* xn, void* M, int digits, const void* ctx,
                   hipStream_t st);
 void matrix_batch_launch(const KernelEntry& k, int real, const MatTile* tiles, int64_t ntiles, const void* xt, const void* xs, const void* xn, void* M,

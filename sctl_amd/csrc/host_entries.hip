@@ -251,6 +251,33 @@ int sctl_amd_eval_grad_host(int kernel, int real, int64_t Nt, int64_t Ns, const 
   return rc ? rc : c.finish();
 }
 
+// A null tangent is not declared: no buffer, no transfer, and the driver gets a null pointer for it.
+int sctl_amd_eval_jvp_host(int kernel, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+                           const void* d_trg, const void* d_src, const void* d_nrm, void* dv_trg, int accumulate, int digits, const void* ctx, int ctx_bytes,
+                           int device) {
+  const KernelEntry* k = registry(kernel);
+  int rc = check_jvp(k, real, Nt, Ns, r_trg, r_src, n_src, v_src, d_nrm, dv_trg, ctx_bytes, ctx);
+  if (rc) return rc;
+  if ((rc = check_device(device))) return rc;
+  if (Nt == 0 || Ns == 0) return SCTL_AMD_OK;                  // an empty set: nothing is read or written
+  if (!d_trg && !d_src && !d_nrm && accumulate) return SCTL_AMD_OK;   // the tangent along a zero perturbation: nothing to add
+  const size_t rs = real_size(real);
+  HostCall c(device, real);
+  c.in(0, r_trg, (size_t)Nt * 3 * rs);
+  c.in(1, r_src, (size_t)Ns * 3 * rs);
+  c.in(2, n_src, (size_t)Ns * k->nd * rs);
+  c.in(3, v_src, (size_t)Ns * k->k0 * rs);
+  if (d_trg) c.in(4, d_trg, (size_t)Nt * 3 * rs);
+  if (d_src) c.in(5, d_src, (size_t)Ns * 3 * rs);
+  if (d_nrm) c.in(6, d_nrm, (size_t)Ns * k->nd * rs);
+  c.out(7, dv_trg, (size_t)Nt * k->k1 * rs, HostCall::kZero | HostCall::kStaged | (accumulate ? HostCall::kAccumulate : 0));
+  rc = c.start();
+  if (rc == SCTL_AMD_OK)
+    rc = eval_jvp_device(*k, real, Nt, Ns, c.dev(0), c.dev(1), k->nd ? c.dev(2) : nullptr, c.dev(3), d_trg ? c.dev(4) : nullptr, d_src ? c.dev(5) : nullptr,
+                         d_nrm ? c.dev(6) : nullptr, c.dev(7), digits, ctx, c.st);
+  return rc ? rc : c.finish();
+}
+
 // nd == 1 goes through the single gradient entry (bit-identical results); nd == 0 is a no-op after the argument checks.
 // Coordinates and normals go down once, the nd density rows and the nd weight rows in one transfer each; the outputs do not grow with nd.
 int sctl_amd_eval_grad_densities_host(int kernel, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,

@@ -1,0 +1,8 @@
+// Tangent (directional-derivative) evaluation kernels of Laplace3D_FDxUdU (jvp_kernel.hpp): fp64 modes 0-2, fp32 modes 0-1.
+#include "jvp_kernel.hpp"
+namespace sctl_amd {
+const JvpEntry& jvp_Laplace3D_FDxUdU() {
+  static const JvpEntry e = make_jvp_entry<Laplace3D_FDxUdU>();
+  return e;
+}
+}  // namespace sctl_amd

@@ -47,6 +47,8 @@ int check_grad(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const voi
                const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx);
 int check_grad_densities(const KernelEntry* k, int real, int nd, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src,
                          const void* v_src, const void* w_trg, const void* g_nrm, int ctx_bytes, const void* ctx);
+int check_jvp(const KernelEntry* k, int real, int64_t Nt, int64_t Ns, const void* r_trg, const void* r_src, const void* n_src, const void* v_src,
+              const void* d_nrm, const void* dv_trg, int ctx_bytes, const void* ctx);
 int no_device();                                  // SCTL_AMD_ERR_NO_DEVICE with the text every entry gives
 int check_device(int device);                      // ... and a device index within the devices there are
 
